@@ -10,6 +10,11 @@ Streams are independent (data parallel): stream s runs on rank s // B; the only 
 of the weight arena from rank 0 at start-up ("scaling": "weak").
 
 value = audio seconds processed by all ranks / max-over-ranks wall time  (x real time = 1 / RTF).
+
+A plain run sets up, warms up, times --steps steps and prints the headline line (ms_per_step = wall time of one timed
+step); --dump-outputs DIR also writes the last timed step's results as DIR/<name>.npy.  --full adds, after the timed
+steps, everything reported beside the headline: roofline, decode mode, encoder / log-mel / VAD replays, the streaming
+latency lines and the CPU baseline.
 """
 from __future__ import annotations
 
@@ -83,7 +88,17 @@ def parse():
     p.add_argument("--dry-run", action="store_true",
                    help="CPU rehearsal of the launch / rendezvous / broadcast / max-over-ranks plumbing (gloo, no GPU)")
     p.add_argument("--no-stream", action="store_true", help="skip the per-stream process_iter latency lines")
-    return p.parse_args()
+    p.add_argument("--full", action="store_true",
+                   help="after the timed steps, also measure and report everything beside the headline: the roofline "
+                        "of the dominant kernel family, decode mode, encoder / log-mel / VAD replays, the streaming "
+                        "latency lines and the CPU baseline (--no-stream / --no-cpu-baseline drop those two again)")
+    p.add_argument("--dump-outputs", metavar="DIR",
+                   help="write what the last timed step returned (every window's tokens, language, log-probabilities, "
+                        "no-speech probability and word-alignment times) as DIR/<name>.npy, float32")
+    args = p.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        p.error("--steps must be >= 1 and --warmup >= 0")
+    return args
 
 
 # WMX_* variables a measured line may run under: documented knobs that select a configuration the line then reports
@@ -349,6 +364,38 @@ def vad_bench(streams):
     return {"calls": res, "note": "wall clock per wmx_vad_process (H2D + 2 launches + D2H + sync), synthetic weights"}
 
 
+def dump_outputs(out_dir, res, max_new_tokens, world=1, rank=0):
+    """--dump-outputs: what one step returned to its caller (the WindowResult of every window of this rank, in stream
+    order), one float32 array per field as out_dir/<name>.npy (<name>.rank<r>.npy on ranks above 0).  Ragged fields
+    are padded with -1 to the longest a window can be (token ids and counts are exact in float32); a few kB in all."""
+    B = len(res)
+
+    def padded(rows, width):
+        width = max([width] + [len(r) for r in rows if r is not None])
+        a = np.full((B, width), -1.0, np.float32)
+        for i, r in enumerate(rows):
+            if r is not None:
+                a[i, :len(r)] = np.asarray(r, np.float32)
+        return a
+
+    arrays = {
+        "tokens": padded([r.tokens for r in res], max_new_tokens),
+        "n_tokens": np.array([len(r.tokens) for r in res], np.float32),
+        "language": np.array([r.language for r in res], np.float32),
+        "language_prob": np.array([r.language_prob for r in res], np.float32),
+        "sum_logprob": np.array([r.sum_logprob for r in res], np.float32),
+        "avg_logprob": np.array([r.avg_logprob for r in res], np.float32),
+        "no_speech_prob": np.array([r.no_speech_prob for r in res], np.float32),
+        "seek_frames": np.array([r.seek_frames for r in res], np.float32),
+        "jump_times": padded([r.jump_times for r in res], max_new_tokens + 1),
+        "text_token_probs": padded([r.text_token_probs for r in res], max_new_tokens),
+    }
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, f"{name}.npy" if rank == 0 else f"{name}.rank{rank}.npy"), a)
+    return sorted(arrays)
+
+
 def dry_run(args):
     """The multi-rank plumbing of main() without a GPU: gloo rendezvous, the arena broadcast, barrier-bracketed
     timed steps, max over ranks, one JSON line from rank 0 (tests/test_bench_launch.py drives it at world 2)."""
@@ -469,6 +516,7 @@ def main():
 
     # in-situ probes captured into each context's decode-step graph: device-clock start / end of the six packed
     # projection GEMMs and the cross attention of the middle decoder layer, at every step of the timed decode loops
+    # (read only by --full, captured in every run: the timed path is the same with and without --full)
     probe_layer = model.dims.n_text_layer // 2
     for g, c in enumerate(ctxs):
         c.set_probe(True, probe_layer)
@@ -500,6 +548,54 @@ def main():
     value = audio_s / elapsed
     ms_per_step = 1000.0 * elapsed / args.steps
     p50 = 1000.0 * float(np.median(lat))
+
+    out = {
+        "metric": METRIC,
+        "value": round(value, 3),
+        "unit": "x_realtime (audio s / wall s, all GPUs)",
+        "n_gpus": world,
+        "steps": args.steps,
+        "warmup": args.warmup,
+        "ms_per_step": round(ms_per_step, 2),
+        "p50_chunk_latency_ms": round(p50, 2),
+        "rtf": round(1.0 / value * world, 6),
+        "chunks_per_s": round(B * world * args.steps / elapsed, 3),
+        "higher_is_better": True,
+        "scaling": "weak",
+        "vs_baseline": None,
+        "dtype": args.dtype,
+        "data": "synthetic (seeded speech-like 30 s audio; build-owned PRNG weights of the named architecture)",
+        "config": {"workload": f"whisper-{args.model} {args.task}, {B} x 30 s windows per GPU, beam {args.beam}, "
+                               f"word_timestamps, language auto-detect, max_new_tokens {args.max_new_tokens}",
+                   "model": f"whisper-{args.model}", "global_batch": B * world, "seq_len": 480000,
+                   "parallelism": f"dp{world} (independent streams)", "decode_steps": steps_done,
+                   "use_graph": not args.no_graph, "context_groups": G,
+                   **({"int8_rule": "int8 weights (CTranslate2's grid and row scales) x 16-bit activations; "
+                                    "CTranslate2's dynamic int8 activation quantisation is not applied "
+                                    "(INTEGRATION.md)"} if args.dtype == "int8" else {})},
+        "stage_ms": [round(s, 2) for s in stages],
+        "env": wmx_env,
+        "lockstep": lockstep,
+        "full": args.full,
+    }
+    if args.dump_outputs:
+        out["dumped_outputs"] = dump_outputs(args.dump_outputs, res, args.max_new_tokens, world, rank)
+    if args.full:
+        # everything beside the headline takes runs of its own (kernel replays, encoder passes, streaming and CPU legs)
+        out.update(full_report(args, model, ctxs, stages, steps_done, res, dt, local, rank, world))
+    if rank == 0:
+        emit(out)
+    D.destroy()
+
+
+def full_report(args, model, ctxs, stages, steps_done, res, dt, local, rank, world):
+    """--full: the figures reported beside the headline, measured after the timed steps (returned as the fields they
+    add to the line)."""
+    from wmx import engine
+    B, G = args.batch, args.groups
+    Bg = B // G
+    ctx = ctxs[0]
+    probe_layer = model.dims.n_text_layer // 2
 
     # roofline of the dominant kernel family.  achieved = ALGORITHMIC bytes / launch duration; the duration is
     # measured in situ over the timed region by device-clock probes on every launch of layer `probe_layer` (and the
@@ -701,33 +797,7 @@ def main():
     log(f"[rank {rank}] replayed kernel us/launch: " + ", ".join(f"{k}={1000 * v[0]:.2f}" for k, v in kern_stats.items()))
 
     out = {
-        "metric": METRIC,
-        "value": round(value, 3),
-        "unit": "x_realtime (audio s / wall s, all GPUs)",
-        "n_gpus": world,
-        "steps": args.steps,
-        "warmup": args.warmup,
-        "ms_per_step": round(ms_per_step, 2),
-        "p50_chunk_latency_ms": round(p50, 2),
-        "rtf": round(1.0 / value * world, 6),
-        "chunks_per_s": round(B * world * args.steps / elapsed, 3),
-        "higher_is_better": True,
-        "scaling": "weak",
-        "vs_baseline": None,
-        "dtype": args.dtype,
-        "data": "synthetic (seeded speech-like 30 s audio; build-owned PRNG weights of the named architecture)",
-        "config": {"workload": f"whisper-{args.model} {args.task}, {B} x 30 s windows per GPU, beam {args.beam}, "
-                               f"word_timestamps, language auto-detect, max_new_tokens {args.max_new_tokens}",
-                   "model": f"whisper-{args.model}", "global_batch": B * world, "seq_len": 480000,
-                   "parallelism": f"dp{world} (independent streams)", "decode_steps": steps_done,
-                   "use_graph": not args.no_graph, "context_groups": G,
-                   **({"int8_rule": "int8 weights (CTranslate2's grid and row scales) x 16-bit activations; "
-                                    "CTranslate2's dynamic int8 activation quantisation is not applied "
-                                    "(INTEGRATION.md)"} if args.dtype == "int8" else {})},
-        "stage_ms": [round(s, 2) for s in stages],
-        "env": wmx_env,
         "decode_mode": decode_mode,
-        "lockstep": lockstep,
         "roofline": roof,
         "encoder": encoder,
         "logmel": logmel,
@@ -763,9 +833,7 @@ def main():
         except Exception as e:  # the baseline is reported, never the target
             log(f"[cpu] baseline failed: {e!r}")
             out["cpu_baseline"] = None
-    if rank == 0:
-        emit(out)
-    D.destroy()
+    return out
 
 
 if __name__ == "__main__":

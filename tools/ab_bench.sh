@@ -15,7 +15,7 @@ for r in $(seq 1 "$R"); do
     lib=$PWD/realtime-whisper-asr_amd/wmx/libwmx.so
     [ "$n" = base ] || lib=$PWD/realtime-whisper-asr_amd/wmx/libwmx_$n.so
     n=${spec//[@=]/_}
-    env WMX_LIB=$lib $kv timeout -k 10 300 python bench.py --no-cpu-baseline --no-stream > "$O/${n}_$r.json" 2> "$O/${n}_$r.err" \
+    env WMX_LIB=$lib $kv timeout -k 10 300 python bench.py --full --no-cpu-baseline --no-stream > "$O/${n}_$r.json" 2> "$O/${n}_$r.err" \
       || { echo "$n round $r failed"; exit 1; }
     python - "$O/${n}_$r.json" "$n" "$r" <<'EOF'
 import json, sys

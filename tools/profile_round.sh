@@ -14,11 +14,11 @@ mkdir -p "$O"
 timeout -k 10 600 python "$R/tools/pmc_traffic.py" dec_qkv dec_proj dec_fc1 dec_fc2 reduce_ln cross_attn --batch 4 \
   --out "$O/pmc_traffic.json" > "$O/pmc.log" 2>&1 || exit 1
 cp "$O/pmc_traffic.json" "$R/profiles/${ROUND}_pmc_traffic.json" || exit 1
-timeout -k 10 400 python "$R/bench.py" > "$O/bench_default.log" 2>&1 || exit 1
+timeout -k 10 400 python "$R/bench.py" --full > "$O/bench_default.log" 2>&1 || exit 1
 cd /tmp && export TMPDIR=/tmp
 rm -rf /tmp/prof_$TAG
 timeout -k 10 500 rocprofv3 --kernel-trace --stats -d /tmp/prof_$TAG -o run --output-format csv -- \
-  python3 "$R/bench.py" --no-cpu-baseline --no-stream > "$O/bench_rocprof.log" 2>&1 || exit 1
+  python3 "$R/bench.py" --full --no-cpu-baseline --no-stream > "$O/bench_rocprof.log" 2>&1 || exit 1
 KS=$(find /tmp/prof_$TAG -name "run_kernel_stats.csv" -print -quit)
 DS=$(find /tmp/prof_$TAG -name "run_domain_stats.csv" -print -quit)
 KT=$(find /tmp/prof_$TAG -name "run_kernel_trace.csv" -print -quit)

@@ -31,10 +31,10 @@ case "${2:-quick}" in
       > "$O/gputest_k.log" 2>&1
     rc=$?; tail -3 "$O/gputest_k.log"; exit $rc ;;
   bench)
-    timeout -k 10 400 python bench.py > "$O/bench_default.json" 2> "$O/bench_default.err" || { echo bench failed; exit 1; }
+    timeout -k 10 400 python bench.py --full > "$O/bench_default.json" 2> "$O/bench_default.err" || { echo bench failed; exit 1; }
     head -c 400 "$O/bench_default.json"; echo ;;
   quick)
-    timeout -k 10 300 python bench.py --no-cpu-baseline --no-stream > "$O/bench_quick.json" 2> "$O/bench_quick.err" \
+    timeout -k 10 300 python bench.py --full --no-cpu-baseline --no-stream > "$O/bench_quick.json" 2> "$O/bench_quick.err" \
       || { echo bench failed; exit 1; }
     head -c 400 "$O/bench_quick.json"; echo ;;
 esac

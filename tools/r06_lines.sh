@@ -10,7 +10,7 @@ HB=$!
 trap "kill $HB" EXIT
 for spec in "fp8_b16:--dtype fp8 --task translate --batch 16" "bf16_b16:--task translate --batch 16" "int8:--dtype int8"; do
   n=${spec%%:*}; a=${spec#*:}
-  timeout -k 10 400 python bench.py --no-cpu-baseline --no-stream $a > "$O/bench_$n.json" 2> "$O/bench_$n.err" || { echo "$n failed"; exit 1; }
+  timeout -k 10 400 python bench.py --full --no-cpu-baseline --no-stream $a > "$O/bench_$n.json" 2> "$O/bench_$n.err" || { echo "$n failed"; exit 1; }
   python - "$O/bench_$n.json" "$n" <<'PY'
 import json, sys
 d = json.loads(open(sys.argv[1]).read().strip().splitlines()[-1])
