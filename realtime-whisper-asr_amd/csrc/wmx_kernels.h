@@ -259,7 +259,7 @@ void launch_unpack_packed(const uint16_t* packed, uint16_t* rowmajor, int N, int
 // decode step (Tn == 1): x = embed, out16 = LN(x) * g + b, in one launch
 void launch_embed_ln(DT dt, const uint16_t* tok_emb, const uint16_t* pos_emb, const int* hist, long hist_ld, int R,
                      const int* pad, const int* slot0, const float* g, const float* b, int d, float* x, uint16_t* out,
-                     hipStream_t st, int V, float2* stats = nullptr, long stats_ld = 0);
+                     hipStream_t st, int V);
 // LayerNorm (g, b) folded into the projection W (+ bias): packed Wp = W diag(g), c1 = Wp 1, c2 = bias + W b
 // (rowmajor: Wp is written row-major [N][K] instead of packed: the encoder's gemm256 operand)
 void launch_fold_ln(DT dt, const uint16_t* Wrm, const float* g, const float* b, const float* bias, int N, int K,

@@ -567,16 +567,13 @@ void launch_unpack_packed(const uint16_t* packed, uint16_t* rowmajor, int N, int
 
 // ---------------- decode step: token + position embedding and the first layer's LN1 in one launch ----------------
 // one wave per row (4 rows per workgroup); the same arithmetic as embed_kernel followed by layernorm_kernel
-// stats != null (LayerNorm folded into the projections): out = the 16-bit copy of x, stats[g][r] = (mean, M2) of
-// each aligned 16-column group g of x (wmx_common.h row_ln_from_stats), no LN here
 template <DT T>
 __global__ __launch_bounds__(256) void embed_ln_kernel(const uint16_t* __restrict__ tok_emb,
                                                        const uint16_t* __restrict__ pos_emb, const int* __restrict__ hist,
                                                        long hist_ld, const int* __restrict__ pad,
                                                        const int* __restrict__ slot0, const float* __restrict__ g,
                                                        const float* __restrict__ bb, int rows, int d,
-                                                       float* __restrict__ x, uint16_t* __restrict__ out,
-                                                       float2* __restrict__ stats, long stats_ld, int V) {
+                                                       float* __restrict__ x, uint16_t* __restrict__ out, int V) {
   const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
   const int r = blockIdx.x * 4 + wave;
   if (r >= rows) return;
@@ -600,24 +597,6 @@ __global__ __launch_bounds__(256) void embed_ln_kernel(const uint16_t* __restric
     } else {
       v[i] = make_float4(0.f, 0.f, 0.f, 0.f);
     }
-  }
-  if (stats) {  // per 16-column group = 4 consecutive quads = an aligned group of 4 lanes (d % 64 == 0)
-    uint16_t* o = out + (long)r * d;
-#pragma unroll
-    for (int i = 0; i < 8; ++i) {
-      if (i * 64 >= n4) break;  // wave-uniform
-      const int c = lane + i * 64;
-      const float4 a = v[i];
-      const float mg = sum4_lanes((a.x + a.y) + (a.z + a.w)) * (1.f / 16.f);
-      const float dx = a.x - mg, dy = a.y - mg, dz = a.z - mg, dw = a.w - mg;
-      const float m2 = sum4_lanes((dx * dx + dy * dy) + (dz * dz + dw * dw));
-      if (c < n4) {
-        const u16x4 h = {from_f32<T>(a.x), from_f32<T>(a.y), from_f32<T>(a.z), from_f32<T>(a.w)};
-        reinterpret_cast<u16x4*>(o)[c] = h;
-        if ((c & 3) == 0) stats[(long)(c >> 2) * stats_ld + r] = make_float2(mg, m2);
-      }
-    }
-    return;
   }
   const float mean = wave_sum(s) / d;
   float q = 0.f;
@@ -649,15 +628,15 @@ __global__ __launch_bounds__(256) void embed_ln_kernel(const uint16_t* __restric
 
 void launch_embed_ln(DT dt, const uint16_t* tok_emb, const uint16_t* pos_emb, const int* hist, long hist_ld, int R,
                      const int* pad, const int* slot0, const float* g, const float* b, int d, float* x, uint16_t* out,
-                     hipStream_t st, int V, float2* stats, long stats_ld) {
-  WMX_CHECK(d % 32 == 0 && d <= 2048 && (!stats || d % 64 == 0) && V >= 1, "embed_ln: d");
+                     hipStream_t st, int V) {
+  WMX_CHECK(d % 32 == 0 && d <= 2048 && V >= 1, "embed_ln: d");
   dim3 grid(cdiv(R, 4));
   if (dt == DT::BF16)
     hipLaunchKernelGGL(embed_ln_kernel<DT::BF16>, grid, dim3(256), 0, st, tok_emb, pos_emb, hist, hist_ld, pad, slot0,
-                       g, b, R, d, x, out, stats, stats_ld, V);
+                       g, b, R, d, x, out, V);
   else
     hipLaunchKernelGGL(embed_ln_kernel<DT::F16>, grid, dim3(256), 0, st, tok_emb, pos_emb, hist, hist_ld, pad, slot0,
-                       g, b, R, d, x, out, stats, stats_ld, V);
+                       g, b, R, d, x, out, V);
   WMX_HIP(hipGetLastError());
 }
 

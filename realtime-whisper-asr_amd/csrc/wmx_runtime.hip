@@ -182,14 +182,13 @@ struct Model {
   float* mel_w = nullptr;
   bool initialized = false;
   bool dirty = false;  // a tensor was set since the derived copies (row-major, MX-fp8, folded) were made
-  bool fold = false;   // decode step on the LayerNorm-folded projections (WMX_FOLD=1; default: reduce_ln form)
-  // the mixed decode step (dec_step_mixed): the d x d residual producers (out-proj, cross-out) unsplit with row
+  // the mixed decode step (dec_step_as): the d x d residual producers (out-proj, cross-out) unsplit with row
   // statistics and LN2 / LN3 folded into their consumers (the fused cross-q projection, fc1); fc2 stays split-K +
   // reduce_ln.  16-bit models only (the fp8 decode keeps the fast step)
+  bool mixed = false;
   // encoder: the two LayerNorms of every layer folded into qkv / fc1 (the residual producers leave x's 16-bit copy
   // and per-256-column statistics); 16-bit models with a width multiple of 256 (WMX_ENC_FOLD=0 turns it off)
   bool enc_fold = false;
-  bool mixed = false;
   hipStream_t st = nullptr;
 };
 
@@ -979,10 +978,21 @@ struct W8 {
   const float* s8 = nullptr;
   bool i8 = false;  // int8 bytes (the CTranslate2 grid) instead of e4m3
 };
-static void set_w(PackedCall& g, const uint16_t* Wp, W8 w8) {
+// the packed-GEMM launch every decoder projection builds on: operands, shape, the in-situ probe of the launch being
+// issued; the callers add what is theirs (epilogue, split count and partials, tile width)
+static PackedCall packed_call(const Ctx& c, const uint16_t* A, long lda, const uint16_t* Wp, W8 w8, int M, int N, int K) {
+  PackedCall g{};
+  g.A = A;
+  g.lda = lda;
   g.W = w8.q8 ? reinterpret_cast<const uint16_t*>(w8.q8) : Wp;
   g.wscale = w8.q8 ? w8.s8 : nullptr;
   g.w8kind = w8.i8 ? 2 : 1;
+  g.M = M;
+  g.N = N;
+  g.K = K;
+  g.tprobe = c.cur_probe;
+  g.pslot = c.slot;
+  return g;
 }
 
 static void gemm_p(Ctx& c, const uint16_t* A, long lda, const uint16_t* Wp, int M, int N, int K, const Epi& e,
@@ -991,37 +1001,23 @@ static void gemm_p(Ctx& c, const uint16_t* A, long lda, const uint16_t* Wp, int 
     gemm(c, A, lda, Wrm, K, M, N, K, e);
     return;
   }
-  PackedCall g;
-  g.A = A;
-  g.lda = lda;
-  set_w(g, Wp, w8);
-  g.M = M;
-  g.N = N;
-  g.K = K;
-  g.S = 1;
+  PackedCall g = packed_call(c, A, lda, Wp, w8, M, N, K);
   g.epi = e;
-  g.tprobe = c.cur_probe;
-  g.pslot = c.slot;
   launch_gemm_packed(c.dt, g, c.st);
+}
+
+// split count of a partial-output launch: nothing to split is still written as two raw partials
+static int part_splits(int M, int N, int K, long cap_elems) {
+  const int S = packed_splits(M, N, K, cap_elems);
+  return S == 1 ? 2 : S;
 }
 
 // decoder projection on packed weights, split-K raw partials into c.part; returns the split count
 static int gemm_p_part(Ctx& c, const uint16_t* A, long lda, const uint16_t* Wp, int M, int N, int K, W8 w8 = {}) {
-  PackedCall g;
-  g.A = A;
-  g.lda = lda;
-  set_w(g, Wp, w8);
-  g.M = M;
-  g.N = N;
-  g.K = K;
-  g.S = packed_splits(M, N, K, c.part_elems);
+  PackedCall g = packed_call(c, A, lda, Wp, w8, M, N, K);
+  g.S = part_splits(M, N, K, c.part_elems);
   g.part = c.part;
-  g.tprobe = c.cur_probe;
-  g.pslot = c.slot;
-  if (g.S == 1) {  // nothing to split: a single slice is still written as raw partials
-    g.S = 2;
-    WMX_CHECK(2L * M * N <= c.part_elems, "decode gemm: partial buffer too small");
-  }
+  WMX_CHECK((long)g.S * M * N <= c.part_elems, "decode gemm: partial buffer too small");
   launch_gemm_packed(c.dt, g, c.st);
   return g.S;
 }
@@ -1062,9 +1058,35 @@ static void gemm_mx8(Ctx& c, const uint8_t* A, const uint8_t* AS, const uint8_t*
   launch_gemm_mx8(c.dt, g, c.st);
 }
 
+// encoder self attention of B windows over the fused q / k / v rows in c.eqkv; mx8: the output also as MX-fp8
+// (bytes + block scales), the A operand of the MX-fp8 out-projection
+static AttnArgs enc_attn_args(const Ctx& c, int B, bool mx8) {
+  const int da = c.m->d.n_audio_state;
+  AttnArgs a{};
+  a.q = c.eqkv;
+  a.k = c.eqkv + da;
+  a.v = c.eqkv + 2 * da;
+  a.q_ld = a.k_ld = a.v_ld = 3 * da;
+  a.q_bstride = a.k_bstride = a.v_bstride = 1500L * 3 * da;
+  a.o = c.eao;
+  a.o_ld = da;
+  a.o_bstride = 1500L * da;
+  a.B = B;
+  a.H = c.m->d.n_audio_head;
+  a.Tq = a.Tk = 1500;
+  a.head_stride = 64;
+  if (mx8) {
+    a.o8 = c.ea8;
+    a.os = c.ea8s;
+    a.o8_ld = da;
+    a.os_ld = da / 32;
+  }
+  return a;
+}
+
 static void encode_layers_mx8(Ctx& c, int B) {
   Model& m = *c.m;
-  const int da = m.d.n_audio_state, H = m.d.n_audio_head;
+  const int da = m.d.n_audio_state;
   const int rows = B * 1500;
   for (auto& L : m.enc) {
     launch_layernorm_mx8(c.ex, L.ln1g, L.ln1b, c.eh8, c.eh8s, rows, da, c.st);
@@ -1074,24 +1096,7 @@ static void encode_layers_mx8(Ctx& c, int B) {
     eq.out = c.eqkv;
     eq.ldc = 3L * da;
     gemm_mx8(c, c.eh8, c.eh8s, L.qkv8, L.qkv8s, rows, 3 * da, da, eq);
-    AttnArgs a{};
-    a.q = c.eqkv;
-    a.k = c.eqkv + da;
-    a.v = c.eqkv + 2 * da;
-    a.q_ld = a.k_ld = a.v_ld = 3 * da;
-    a.q_bstride = a.k_bstride = a.v_bstride = 1500L * 3 * da;
-    a.o = c.eao;
-    a.o_ld = da;
-    a.o_bstride = 1500L * da;
-    a.B = B;
-    a.H = H;
-    a.Tq = a.Tk = 1500;
-    a.head_stride = 64;
-    a.o8 = c.ea8;
-    a.os = c.ea8s;
-    a.o8_ld = da;
-    a.os_ld = da / 32;
-    launch_attn_encoder(c.dt, a, c.st);
+    launch_attn_encoder(c.dt, enc_attn_args(c, B, true), c.st);
     Epi eo;
     eo.kind = EPI_RESID32;
     eo.bias = L.bo;
@@ -1148,7 +1153,7 @@ static Epi epi_lnf(Ctx& c, int kind, const float* c1, const float* c2, void* out
 
 static void encode(Ctx& c, int B) {
   Model& m = *c.m;
-  const int da = m.d.n_audio_state, H = m.d.n_audio_head, M = m.d.n_mels;
+  const int da = m.d.n_audio_state, M = m.d.n_mels;
   const long rows = (long)B * 1500;
   const bool fold = !m.mx8 && enc_fold_rows(c, rows);
   launch_im2col_conv1(c.dt, c.mel, B, M, m.K1p, c.im1, c.st);
@@ -1172,20 +1177,7 @@ static void encode(Ctx& c, int B) {
       launch_layernorm(c.dt, c.ex, L.ln1g, L.ln1b, c.ehb, (int)rows, da, c.st);
       gemm(c, c.ehb, da, L.wqkv, da, (int)rows, 3 * da, da, epi(EPI_STORE16, L.bqkv, c.eqkv, 3 * da));
     }
-    AttnArgs a{};
-    a.q = c.eqkv;
-    a.k = c.eqkv + da;
-    a.v = c.eqkv + 2 * da;
-    a.q_ld = a.k_ld = a.v_ld = 3 * da;
-    a.q_bstride = a.k_bstride = a.v_bstride = 1500L * 3 * da;
-    a.o = c.eao;
-    a.o_ld = da;
-    a.o_bstride = 1500L * da;
-    a.B = B;
-    a.H = H;
-    a.Tq = a.Tk = 1500;
-    a.head_stride = 64;
-    launch_attn_encoder(c.dt, a, c.st);
+    launch_attn_encoder(c.dt, enc_attn_args(c, B, false), c.st);
     if (fold) {
       gemm(c, c.eao, da, L.wo, da, (int)rows, da, da, epi_lns(c, EPI_RESID32_LNS, L.bo, rows));
       gemm(c, c.ehb, da, L.ffc1, da, (int)rows, 4 * da, da,
@@ -1266,122 +1258,177 @@ struct FwdArgs {
   int win_rows = 0;  // decode step: rows per window of the cross attention (0: the context's beam width)
 };
 
-// Decode step (Tn == 1): every projection runs on packed weights with split-K partials, and the reductions are
-// fused into the consumers -- q/k/v into self attention (which also writes the KV cache), cross q into cross
-// attention, out-proj / fc2 into reduce_ln (residual add + the next LayerNorm).  10 launches per layer.
-// Leaves LN_final(x) of every row in c.dhb.
-static void dec_step_fast(Ctx& c, const FwdArgs& f) {
-  Model& m = *c.m;
-  const int dt = m.d.n_text_state, H = m.d.n_text_head, Lt = m.d.n_text_layer;
-  const int R = f.rows;
-  const size_t cache_layer = (size_t)c.Tctx * c.R * dt;
-  launch_embed_ln(c.dt, m.tok_emb, m.dec_pos, f.tok, f.tok_ld, R, f.pad_seq, c.slot, m.dec[0].ln1g, m.dec[0].ln1b, dt,
-                  c.dx, c.dhb, c.st, m.d.n_vocab);
-  const size_t probe_stride = (size_t)c.Tctx * kProbeWG * 2;
-  for (int l = 0; l < Lt; ++l) {
-    DecLayer& L = m.dec[l];
-    const bool last = l + 1 == Lt;
-    const bool probed = c.probe_kernel >= 0 && l == c.probe_layer;
-    const bool prev = c.probe_kernel >= 0 && l + 1 == c.probe_layer;  // its last launch precedes the probed qkv
-    auto probe = [&](int id) { c.cur_probe = probed ? c.probe_buf + id * probe_stride : nullptr; };
-    auto pbuf = [&](int id) { return probed ? c.probe_buf + id * probe_stride : nullptr; };
-    // self attention: QKV partials -> (reduce, cache write, attention) -> out-proj partials -> +x, LN2
-    probe(kProbeQKV);
-    int S = gemm_p_part(c, c.dhb, dt, L.wqkv, R, 3 * dt, dt, w8_of(m, L.q8qkv, L.s8qkv));
-    c.cur_probe = nullptr;
-    DecAttnArgs a{};
-    a.o = c.dao;
-    a.R = R;
-    a.Tn = 1;
-    a.H = H;
-    a.d = dt;
-    a.kc = c.kc + l * cache_layer;
-    a.vc = c.vc + l * cache_layer;
-    a.kv_R = c.R;
-    a.anc = f.anc;
-    a.anc_ld = c.Tctx;
-    a.pad = f.pad_seq;
-    a.slot0 = c.slot;
-    a.qpart = c.part;
-    a.qS = S;
-    a.qpart_stride = (long)R * 3 * dt;
-    a.qpart_ld = 3 * dt;
-    a.qbias = L.bqkv;
-    a.tprobe = pbuf(kProbeSelf);
-    launch_self_attn(c.dt, a, c.st);
-    probe(kProbeOut);
-    gemm_p_redln(c, c.dao, dt, L.wo, R, dt, dt, L.bo, L.ln2g, L.ln2b, pbuf(kProbeRedOut), w8_of(m, L.q8o, L.s8o));
-    // cross attention: q partials -> (reduce, attention) -> out-proj partials -> +x, LN3; with c.xq_fused the
-    // cross attention projects its own queries from LN2(x) (no cross-q launch)
-    if (!c.xq_fused) {
-      probe(kProbeCrossQ);
-      S = gemm_p_part(c, c.dhb, dt, L.wcq, R, dt, dt, w8_of(m, L.q8cq, L.s8cq));
-      c.cur_probe = nullptr;
-    }
-    DecAttnArgs x{};
-    x.o = c.dao;
-    x.R = R;
-    x.Tn = 1;
-    x.H = H;
-    x.d = dt;
-    set_cross_images(c, x, l);
-    x.Tk = 1500;
-    x.rows_per_win = f.win_rows > 0 ? f.win_rows : c.K;
-    x.qpart = c.part;
-    x.qS = S;
-    x.qpart_stride = (long)R * dt;
-    x.qpart_ld = dt;
-    x.qbias = L.bcq;
-    if (c.xq_fused) {
-      x.qS = 0;
-      x.wq = m.kv8 ? reinterpret_cast<const uint16_t*>(L.q8cq) : L.wcq;
-      x.wq_scale = m.kv8 ? L.s8cq : nullptr;
-      x.qin = c.dhb;
-      x.qin_ld = dt;
-    }
-    x.xcnt = c.xa_cnt;
-    x.slot0 = c.slot;
-    if (probed) x.tprobe = c.probe_buf + kProbeCross * probe_stride;
-    launch_cross_attn(c.dt, x, c.xa_ws, c.st);
-    probe(kProbeCrossOut);
-    gemm_p_redln(c, c.dao, dt, L.wco, R, dt, dt, L.bco, L.ln3g, L.ln3b, pbuf(kProbeRedCrossOut),
-                 w8_of(m, L.q8co, L.s8co));
-    // MLP: fc1 (+bias, GELU in-kernel) -> fc2 partials -> +x, next LN1 (or the final LN)
-    probe(kProbeFc1);
-    gemm_p(c, c.dhb, dt, L.wfc1, R, 4 * dt, dt, epi(EPI_GELU16, L.bfc1, c.df1, 4 * dt), nullptr,
-           w8_of(m, L.q8fc1, L.s8fc1));
-    probe(kProbeFc2);
-    gemm_p_redln(c, c.df1, 4 * dt, L.wfc2, R, dt, 4 * dt, L.bfc2, last ? m.lng : m.dec[l + 1].ln1g,
-                 last ? m.lnb : m.dec[l + 1].ln1b,
-                 probed ? pbuf(kProbeRedFc2) : prev ? c.probe_buf + kProbePrev * probe_stride : nullptr,
-                 w8_of(m, L.q8fc2, L.s8fc2));
-    c.cur_probe = nullptr;
+// the two shapes a forward takes: a decode step over every row of B windows (tokens and pads per row, the cache
+// gathered through the ancestry table when beams reorder) ...
+static FwdArgs fwd_step(const Ctx& c, int B) {
+  FwdArgs f{};
+  f.rows = c.K * B;
+  f.Tn = 1;
+  f.rmul = 1;
+  f.tok = c.hist;
+  f.tok_ld = c.Tctx;
+  f.pad_seq = c.pad_row;
+  f.prefill = false;
+  f.anc = c.beam ? c.anc : nullptr;
+  return f;
+}
+// ... and Tn tokens of one sequence per window, in the window's first row (cache row b * K): tok = c.hist or
+// c.hist_tmp, pad_seq per window or null
+static FwdArgs fwd_prefill(const Ctx& c, int B, int Tn, const int* tok, const int* pad_seq) {
+  FwdArgs f{};
+  f.rows = B;
+  f.Tn = Tn;
+  f.rmul = c.K;
+  f.tok = tok;
+  f.tok_ld = (long)c.K * c.Tctx;
+  f.pad_seq = pad_seq;
+  f.prefill = true;
+  f.anc = nullptr;
+  return f;
+}
+
+// ---- the decoder's attention launches, each kind built in one place ----
+static DecAttnArgs dec_attn_args(const Ctx& c, int rows, int Tn) {
+  DecAttnArgs a{};
+  a.R = rows;
+  a.Tn = Tn;
+  a.H = c.m->d.n_text_head;
+  a.d = c.m->d.n_text_state;
+  return a;
+}
+
+// decode self attention of layer l: one new token per row at *slot, the cache gathered through f.anc
+static DecAttnArgs self_attn_args(const Ctx& c, const FwdArgs& f, int l) {
+  DecAttnArgs a = dec_attn_args(c, f.rows, 1);
+  const size_t cache_layer = (size_t)c.Tctx * c.R * a.d;
+  a.o = c.dao;
+  a.kc = c.kc + l * cache_layer;
+  a.vc = c.vc + l * cache_layer;
+  a.kv_R = c.R;
+  a.anc = f.anc;
+  a.anc_ld = c.Tctx;
+  a.pad = f.pad_seq;
+  a.slot0 = c.slot;
+  return a;
+}
+// ... q / k / v summed from the S split-K partials of the QKV launch (the decode step; writes k / v to the cache)
+static DecAttnArgs self_attn_from_parts(const Ctx& c, const FwdArgs& f, int l, int S) {
+  DecAttnArgs a = self_attn_args(c, f, l);
+  a.qpart = c.part;
+  a.qS = S;
+  a.qpart_stride = (long)f.rows * 3 * a.d;
+  a.qpart_ld = 3 * a.d;
+  a.qbias = c.m->dec[l].bqkv;
+  return a;
+}
+// ... q projected into c.dq, k / v already in the cache (EPI_QKV_CACHE)
+static DecAttnArgs self_attn_from_q(const Ctx& c, const FwdArgs& f, int l) {
+  DecAttnArgs a = self_attn_args(c, f, l);
+  a.q = c.dq;
+  a.q_ld = a.d;
+  return a;
+}
+
+// where a cross attention takes its queries from: Rows = projected into c.dcq; Parts = the S split-K partials of the
+// cross-q launch; Fused = projected inside the launch from LN2(x) in c.dhb; FusedLN = projected inside from x's
+// 16-bit copy in c.dhb through the LN2-folded weights and the row statistics (the mixed step)
+enum class CrossQ { Rows, Parts, Fused, FusedLN };
+static DecAttnArgs cross_attn_args(const Ctx& c, int l, int rows, int Tn, int rows_per_win, CrossQ q, int S = 0) {
+  const Model& m = *c.m;
+  const DecLayer& L = m.dec[l];
+  DecAttnArgs x = dec_attn_args(c, rows, Tn);
+  x.o = c.dao;
+  set_cross_images(c, x, l);
+  x.Tk = 1500;
+  x.rows_per_win = rows_per_win;
+  x.xcnt = c.xa_cnt;
+  if (q == CrossQ::Rows) {
+    x.q = c.dcq;
+    x.q_ld = x.d;
+    return x;
   }
+  x.slot0 = c.slot;  // the decode step's forms
+  if (q != CrossQ::FusedLN) {  // (Fused keeps the partial layout with no slices to sum)
+    x.qpart = c.part;
+    x.qS = q == CrossQ::Parts ? S : 0;
+    x.qpart_stride = (long)rows * x.d;
+    x.qpart_ld = x.d;
+    x.qbias = L.bcq;
+  }
+  if (q != CrossQ::Parts) {
+    x.qin = c.dhb;
+    x.qin_ld = x.d;
+  }
+  if (q == CrossQ::Fused) {
+    x.wq = m.kv8 ? reinterpret_cast<const uint16_t*>(L.q8cq) : L.wcq;
+    x.wq_scale = m.kv8 ? L.s8cq : nullptr;
+  } else if (q == CrossQ::FusedLN) {
+    x.wq = L.fcq;
+    x.ln_c1 = L.c1cq;
+    x.ln_c2 = L.c2cq;
+    x.ln_stats = c.rstat;
+    x.ln_ld = x.d / 16;
+  }
+  return x;
 }
 
-// The mixed step's residual producers: x += acc + bias, its 16-bit copy and per-16-column row statistics
-static Epi epi_resid_stats(Ctx& c, const float* bias, int R) {
-  Epi e = epi(EPI_RESID_STATS, bias, c.dx, c.m->d.n_text_state);
-  e.out16 = c.dhb;
-  e.stats = c.rstat;
-  e.stats_ld = c.m->d.n_text_state / 16;  // row stride of [R][dt / 16]
-  return e;
+// raw scores of layer l's alignment heads over the queries in c.dcq (one sequence per window)
+static DecAttnArgs cross_scores_args(const Ctx& c, const FwdArgs& f, int l) {
+  DecAttnArgs a = dec_attn_args(c, f.rows, f.Tn);
+  a.q = c.dcq;
+  a.q_ld = a.d;
+  set_cross_images(c, a, l);
+  a.Tk = 1500;
+  a.rows_per_win = 1;
+  return a;
 }
 
-static void gemm_p_resid(Ctx& c, const uint16_t* A, long lda, const uint16_t* Wp, int M, int N, int K, const Epi& e) {
-  PackedCall g;
-  g.A = A;
-  g.lda = lda;
-  g.W = Wp;
-  g.M = M;
-  g.N = N;
-  g.K = K;
-  g.S = 1;
-  g.epi = e;
-  g.nct = 1;  // unsplit: 16 columns per workgroup (N / 16 workgroups, 16 waves splitting K)
-  g.tprobe = c.cur_probe;
-  g.pslot = c.slot;
+// prompt prefill: causal flash attention of f.Tn new queries per sequence over layer l's cache (from slot 0)
+static AttnArgs prefill_attn_args(const Ctx& c, const FwdArgs& f, int l) {
+  const int dt = c.m->d.n_text_state;
+  const size_t cache_layer = (size_t)c.Tctx * c.R * dt;
+  AttnArgs a{};
+  a.q = c.dq;
+  a.q_ld = dt;
+  a.q_bstride = (long)f.Tn * dt;
+  a.k = c.kc + l * cache_layer;
+  a.v = c.vc + l * cache_layer;
+  a.k_ld = a.v_ld = (long)c.R * dt;
+  a.k_bstride = a.v_bstride = (long)f.rmul * dt;
+  a.o = c.dao;
+  a.o_ld = dt;
+  a.o_bstride = (long)f.Tn * dt;
+  a.B = f.rows;
+  a.H = c.m->d.n_text_head;
+  a.Tq = f.Tn;
+  a.Tk = f.Tn;  // prefill always starts at slot 0
+  a.head_stride = 64;
+  return a;
+}
+
+// The mixed step's residual producers, unsplit (16 columns per workgroup: N / 16 workgroups, 16 waves splitting K):
+// x += acc + bias, its 16-bit copy -> c.dhb, per-16-column row statistics -> c.rstat
+static void gemm_p_resid_stats(Ctx& c, const uint16_t* A, const uint16_t* Wp, const float* bias, int M, W8 w8) {
+  const int dt = c.m->d.n_text_state;
+  PackedCall g = packed_call(c, A, dt, Wp, w8, M, dt, dt);
+  g.epi = epi(EPI_RESID_STATS, bias, c.dx, dt);
+  g.epi.out16 = c.dhb;
+  g.epi.stats = c.rstat;
+  g.epi.stats_ld = dt / 16;  // row stride of [R][dt / 16]
+  g.nct = 1;
   launch_gemm_packed(c.dt, g, c.st);
+  c.cur_probe = nullptr;
+}
+
+// the mixed step's fc1 epilogue: GELU of the LN3-folded projection, the row statistics merged in the epilogue
+static Epi epi_fc1_lnfold(const Ctx& c, const DecLayer& L) {
+  const int dt = c.m->d.n_text_state;
+  Epi e = epi(EPI_LNFOLD_GELU16, nullptr, c.df1, 4 * dt);
+  e.c1 = L.c1fc1;
+  e.c2 = L.c2fc1;
+  e.stats = c.rstat;
+  e.stats_ld = dt / 16;
+  return e;
 }
 
 // WMX_DEBUG_SYNC=1 (fault localisation on eager, uncaptured steps): synchronise after each launch of the step
@@ -1396,115 +1443,90 @@ static void debug_sync(Ctx& c, const char* what, int l) {
   if (e != hipSuccess) throw std::runtime_error(std::string("debug sync after ") + what + " (layer " + std::to_string(l) + "): " + hipGetErrorString(e));
 }
 
-
-// The mixed decode step: dec_step_fast with the two d x d residual producers of every layer (out-projection,
-// cross out-projection) unsplit -- x += acc + bias, its 16-bit copy and per-16-column row statistics in the GEMM
-// epilogue (EPI_RESID_STATS) -- so their reduce_ln launches go: LN2 is applied by the fused cross-q projection
-// through W diag(g2), c1, c2 (the cross attention merges the row statistics it loads beside its K batch), LN3 by fc1's
-// folded GELU epilogue.  fc2 (K = 4d) keeps split-K partials + reduce_ln (its unsplit form is 15 vs 11 us, DESIGN.md
-// §3), which also produces the next layer's LN1 rows for the split-K QKV.  8 launches per layer instead of 10.
+// Decode step (Tn == 1) in one of two forms.  Both run every projection on packed weights and fuse the reductions
+// into the consumers: q / k / v into self attention (which also writes the KV cache), fc2's split-K partials into
+// reduce_ln (residual add + the next layer's LN1, or the final LN).
+//   fast:  the out-projection and the cross out-projection are split-K too, each followed by reduce_ln (+x, LN2 /
+//          LN3); the cross attention sums the cross-q launch's partials or, with c.xq_fused, projects its own queries
+//          from LN2(x); fc1 applies bias + GELU.  10 launches per layer (11 without xq_fused).
+//   mixed: the two d x d residual producers run unsplit -- x += acc + bias, its 16-bit copy and per-16-column row
+//          statistics in the GEMM epilogue (EPI_RESID_STATS) -- so their reduce_ln launches go: LN2 is applied by the
+//          fused cross-q projection through W diag(g2), c1, c2 (the cross attention merges the row statistics it loads
+//          beside its K batch), LN3 by fc1's folded GELU epilogue.  fc2 (K = 4d) keeps split-K + reduce_ln (its unsplit
+//          form is 15 vs 11 us).  8 launches per layer.  16-bit models with c.xq_fused (dec_step).
 // Leaves LN_final(x) of every row in c.dhb.
-static void dec_step_mixed(Ctx& c, const FwdArgs& f) {
+static void dec_step_as(Ctx& c, const FwdArgs& f, bool mixed) {
   Model& m = *c.m;
-  const int dt = m.d.n_text_state, H = m.d.n_text_head, Lt = m.d.n_text_layer;
+  const int dt = m.d.n_text_state, Lt = m.d.n_text_layer;
   const int R = f.rows;
-  const size_t cache_layer = (size_t)c.Tctx * c.R * dt;
   launch_embed_ln(c.dt, m.tok_emb, m.dec_pos, f.tok, f.tok_ld, R, f.pad_seq, c.slot, m.dec[0].ln1g, m.dec[0].ln1b, dt,
                   c.dx, c.dhb, c.st, m.d.n_vocab);
   const size_t probe_stride = (size_t)c.Tctx * kProbeWG * 2;
+  const CrossQ xq = mixed ? CrossQ::FusedLN : c.xq_fused ? CrossQ::Fused : CrossQ::Parts;
   for (int l = 0; l < Lt; ++l) {
     DecLayer& L = m.dec[l];
     const bool last = l + 1 == Lt;
     const bool probed = c.probe_kernel >= 0 && l == c.probe_layer;
-    const bool prev = c.probe_kernel >= 0 && l + 1 == c.probe_layer;
-    auto probe = [&](int id) { c.cur_probe = probed ? c.probe_buf + id * probe_stride : nullptr; };
+    const bool prev = c.probe_kernel >= 0 && l + 1 == c.probe_layer;  // its last launch precedes the probed qkv
     auto pbuf = [&](int id) { return probed ? c.probe_buf + id * probe_stride : nullptr; };
+    auto probe = [&](int id) { c.cur_probe = pbuf(id); };
     // self attention on LN1(x) (c.dhb): QKV partials -> (reduce, cache write, attention)
     probe(kProbeQKV);
-    const int S = gemm_p_part(c, c.dhb, dt, L.wqkv, R, 3 * dt, dt);
+    int S = gemm_p_part(c, c.dhb, dt, L.wqkv, R, 3 * dt, dt, w8_of(m, L.q8qkv, L.s8qkv));
     c.cur_probe = nullptr;
-    DecAttnArgs a{};
-    a.o = c.dao;
-    a.R = R;
-    a.Tn = 1;
-    a.H = H;
-    a.d = dt;
-    a.kc = c.kc + l * cache_layer;
-    a.vc = c.vc + l * cache_layer;
-    a.kv_R = c.R;
-    a.anc = f.anc;
-    a.anc_ld = c.Tctx;
-    a.pad = f.pad_seq;
-    a.slot0 = c.slot;
-    a.qpart = c.part;
-    a.qS = S;
-    a.qpart_stride = (long)R * 3 * dt;
-    a.qpart_ld = 3 * dt;
-    a.qbias = L.bqkv;
+    DecAttnArgs a = self_attn_from_parts(c, f, l, S);
     a.tprobe = pbuf(kProbeSelf);
     launch_self_attn(c.dt, a, c.st);
-    // out-projection, unsplit: x += o Wo^T + bo, x16 -> c.dhb, row statistics -> c.rstat
+    // out-projection: +x and LN2 (fast), or x, its 16-bit copy and row statistics (mixed)
     probe(kProbeOut);
-    gemm_p_resid(c, c.dao, dt, L.wo, R, dt, dt, epi_resid_stats(c, L.bo, R));
-    c.cur_probe = nullptr;
-    // cross attention with the fused, LN2-folded query projection of x16
-    DecAttnArgs x{};
-    x.o = c.dao;
-    x.R = R;
-    x.Tn = 1;
-    x.H = H;
-    x.d = dt;
-    set_cross_images(c, x, l);
-    x.Tk = 1500;
-    x.rows_per_win = f.win_rows > 0 ? f.win_rows : c.K;
-    x.wq = L.fcq;
-    x.qin = c.dhb;
-    x.qin_ld = dt;
-    x.ln_c1 = L.c1cq;
-    x.ln_c2 = L.c2cq;
-    x.ln_stats = c.rstat;
-    x.ln_ld = dt / 16;
-    x.xcnt = c.xa_cnt;
-    x.slot0 = c.slot;
-    if (probed) x.tprobe = c.probe_buf + kProbeCross * probe_stride;
+    if (mixed)
+      gemm_p_resid_stats(c, c.dao, L.wo, L.bo, R, w8_of(m, L.q8o, L.s8o));
+    else
+      gemm_p_redln(c, c.dao, dt, L.wo, R, dt, dt, L.bo, L.ln2g, L.ln2b, pbuf(kProbeRedOut), w8_of(m, L.q8o, L.s8o));
+    // cross attention; only the fast step without c.xq_fused projects its queries in a launch of their own
+    if (xq == CrossQ::Parts) {
+      probe(kProbeCrossQ);
+      S = gemm_p_part(c, c.dhb, dt, L.wcq, R, dt, dt, w8_of(m, L.q8cq, L.s8cq));
+      c.cur_probe = nullptr;
+    }
+    DecAttnArgs x = cross_attn_args(c, l, R, 1, f.win_rows > 0 ? f.win_rows : c.K, xq, S);
+    x.tprobe = pbuf(kProbeCross);
     launch_cross_attn(c.dt, x, c.xa_ws, c.st);
-    // cross out-projection, unsplit: x += o Wco^T + bco, x16, statistics
+    // cross out-projection: +x and LN3 (fast), or x, its 16-bit copy and row statistics (mixed)
     probe(kProbeCrossOut);
-    gemm_p_resid(c, c.dao, dt, L.wco, R, dt, dt, epi_resid_stats(c, L.bco, R));
-    // MLP: GELU(LN3-folded fc1 of x16) -> fc2 partials -> reduce_ln (x += ..., next layer's LN1 or the final LN)
+    if (mixed)
+      gemm_p_resid_stats(c, c.dao, L.wco, L.bco, R, w8_of(m, L.q8co, L.s8co));
+    else
+      gemm_p_redln(c, c.dao, dt, L.wco, R, dt, dt, L.bco, L.ln3g, L.ln3b, pbuf(kProbeRedCrossOut),
+                   w8_of(m, L.q8co, L.s8co));
+    // MLP: fc1 (+bias, GELU in-kernel; mixed: LN3 folded, no 8-bit copy of the folded weights) -> fc2 partials ->
+    // +x, next LN1 (or the final LN)
     probe(kProbeFc1);
-    Epi e1 = epi(EPI_LNFOLD_GELU16, nullptr, c.df1, 4 * dt);
-    e1.c1 = L.c1fc1;
-    e1.c2 = L.c2fc1;
-    e1.stats = c.rstat;
-    e1.stats_ld = dt / 16;
-    gemm_p(c, c.dhb, dt, L.ffc1, R, 4 * dt, dt, e1);
+    if (mixed)
+      gemm_p(c, c.dhb, dt, L.ffc1, R, 4 * dt, dt, epi_fc1_lnfold(c, L));
+    else
+      gemm_p(c, c.dhb, dt, L.wfc1, R, 4 * dt, dt, epi(EPI_GELU16, L.bfc1, c.df1, 4 * dt), nullptr,
+             w8_of(m, L.q8fc1, L.s8fc1));
     probe(kProbeFc2);
     gemm_p_redln(c, c.df1, 4 * dt, L.wfc2, R, dt, 4 * dt, L.bfc2, last ? m.lng : m.dec[l + 1].ln1g,
                  last ? m.lnb : m.dec[l + 1].ln1b,
-                 probed ? pbuf(kProbeRedFc2) : prev ? c.probe_buf + kProbePrev * probe_stride : nullptr);
+                 probed ? pbuf(kProbeRedFc2) : prev ? c.probe_buf + kProbePrev * probe_stride : nullptr,
+                 w8_of(m, L.q8fc2, L.s8fc2));
     c.cur_probe = nullptr;
   }
 }
 
-static void dec_step(Ctx& c, const FwdArgs& f) {
-  if (c.m->mixed && c.xq_fused)
-    dec_step_mixed(c, f);
-  else
-    dec_step_fast(c, f);
-}
+static void dec_step(Ctx& c, const FwdArgs& f) { dec_step_as(c, f, c.m->mixed && c.xq_fused); }
 
 static void dec_forward(Ctx& c, const FwdArgs& f) {
   Model& m = *c.m;
-  const int dt = m.d.n_text_state, H = m.d.n_text_head, Lt = m.d.n_text_layer;
+  const int dt = m.d.n_text_state, Lt = m.d.n_text_layer;
   const int rowsT = f.rows * f.Tn;
   WMX_CHECK(rowsT <= c.dec_rows_max, "decoder: too many rows");
   launch_embed(c.dt, m.tok_emb, m.dec_pos, f.tok, f.tok_ld, f.rows, f.Tn, f.pad_seq, c.slot, dt, c.dx, c.st, m.d.n_vocab);
   const size_t cache_layer = (size_t)c.Tctx * c.R * dt;
   for (int l = 0; l < Lt; ++l) {
     DecLayer& L = m.dec[l];
-    uint16_t* kcl = c.kc + l * cache_layer;
-    uint16_t* vcl = c.vc + l * cache_layer;
     launch_layernorm(c.dt, c.dx, L.ln1g, L.ln1b, c.dhb, rowsT, dt, c.st);
     Epi eq = epi(EPI_QKV_CACHE, L.bqkv, c.dq, dt);
     eq.d = dt;
@@ -1512,81 +1534,23 @@ static void dec_forward(Ctx& c, const FwdArgs& f) {
     eq.R = c.R;
     eq.rmul = f.rmul;
     eq.slot0 = c.slot;
-    eq.kc = kcl;
-    eq.vc = vcl;
+    eq.kc = c.kc + l * cache_layer;
+    eq.vc = c.vc + l * cache_layer;
     gemm_p(c, c.dhb, dt, L.wqkv, rowsT, 3 * dt, dt, eq, L.rqkv, w8_of(m, L.q8qkv, L.s8qkv));
-    if (f.prefill) {
-      AttnArgs a{};
-      a.q = c.dq;
-      a.q_ld = dt;
-      a.q_bstride = (long)f.Tn * dt;
-      a.k = kcl;
-      a.v = vcl;
-      a.k_ld = a.v_ld = (long)c.R * dt;
-      a.k_bstride = a.v_bstride = (long)f.rmul * dt;
-      a.o = c.dao;
-      a.o_ld = dt;
-      a.o_bstride = (long)f.Tn * dt;
-      a.B = f.rows;
-      a.H = H;
-      a.Tq = f.Tn;
-      a.Tk = f.Tn;  // prefill always starts at slot 0
-      a.head_stride = 64;
-      launch_attn_flash(c.dt, a, 1, 0, f.pad_seq, c.st);
-    } else {
-      DecAttnArgs a{};
-      a.q = c.dq;
-      a.q_ld = dt;
-      a.o = c.dao;
-      a.R = f.rows;
-      a.Tn = 1;
-      a.H = H;
-      a.d = dt;
-      a.kc = kcl;
-      a.vc = vcl;
-      a.kv_R = c.R;
-      a.anc = f.anc;
-      a.anc_ld = c.Tctx;
-      a.pad = f.pad_seq;
-      a.slot0 = c.slot;
-      launch_self_attn(c.dt, a, c.st);
-    }
+    if (f.prefill)
+      launch_attn_flash(c.dt, prefill_attn_args(c, f, l), 1, 0, f.pad_seq, c.st);
+    else
+      launch_self_attn(c.dt, self_attn_from_q(c, f, l), c.st);
     gemm_p(c, c.dao, dt, L.wo, rowsT, dt, dt, epi(EPI_RESID32, L.bo, c.dx, dt), L.ro, w8_of(m, L.q8o, L.s8o));
     launch_layernorm(c.dt, c.dx, L.ln2g, L.ln2b, c.dhb, rowsT, dt, c.st);
     gemm_p(c, c.dhb, dt, L.wcq, rowsT, dt, dt, epi(EPI_STORE16, L.bcq, c.dcq, dt), L.rcq, w8_of(m, L.q8cq, L.s8cq));
-    {
-      DecAttnArgs a{};
-      a.q = c.dcq;
-      a.q_ld = dt;
-      a.o = c.dao;
-      a.R = f.rows;
-      a.Tn = f.Tn;
-      a.H = H;
-      a.d = dt;
-      set_cross_images(c, a, l);
-      a.Tk = 1500;
-      // prefill: one sequence per window; decode through this path: the beams of a window share it
-      a.rows_per_win = f.prefill ? 1 : c.K;
-      a.xcnt = c.xa_cnt;
-      launch_cross_attn(c.dt, a, c.xa_ws, c.st);
-    }
+    // prefill: one sequence per window; decode through this path: the beams of a window share it
+    launch_cross_attn(c.dt, cross_attn_args(c, l, f.rows, f.Tn, f.prefill ? 1 : c.K, CrossQ::Rows), c.xa_ws, c.st);
     if (f.align && c.a_head_cnt[l] > 0) {  // this layer's alignment heads (the device table, alloc_ctx)
       const int nh = c.a_head_cnt[l];
-      {
-        DecAttnArgs a{};
-        a.q = c.dcq;
-        a.q_ld = dt;
-        a.R = f.rows;
-        a.Tn = f.Tn;
-        a.H = H;
-        a.d = dt;
-        set_cross_images(c, a, l);
-        a.Tk = 1500;
-        a.rows_per_win = 1;
-        launch_cross_scores(c.dt, a, c.a_heads + c.a_head_off[l], nh, c.scores, c.st);
-        launch_align_matrix_acc(c.scores, nh, rowsT, 1500, f.Tn, c.a_ntok, c.a_nframes, c.o.median_filter_width,
-                                f.rows, c.st, c.align_out);
-      }
+      launch_cross_scores(c.dt, cross_scores_args(c, f, l), c.a_heads + c.a_head_off[l], nh, c.scores, c.st);
+      launch_align_matrix_acc(c.scores, nh, rowsT, 1500, f.Tn, c.a_ntok, c.a_nframes, c.o.median_filter_width, f.rows,
+                              c.st, c.align_out);
     }
     gemm_p(c, c.dao, dt, L.wco, rowsT, dt, dt, epi(EPI_RESID32, L.bco, c.dx, dt), L.rco, w8_of(m, L.q8co, L.s8co));
     launch_layernorm(c.dt, c.dx, L.ln3g, L.ln3b, c.dhb, rowsT, dt, c.st);
@@ -1598,7 +1562,7 @@ static void dec_forward(Ctx& c, const FwdArgs& f) {
 }
 
 // final LN of selected rows + logits GEMM into c.logits [n][V]
-// (ln_done: c.dhb already holds LN_final of rows 0..n-1, as dec_step_fast leaves it)
+// (ln_done: c.dhb already holds LN_final of rows 0..n-1, as the decode step leaves it)
 static void dec_logits(Ctx& c, const int* rows_idx, int n, bool ln_done = false) {
   Model& m = *c.m;
   const int dt = m.d.n_text_state, V = m.d.n_vocab;
@@ -1726,16 +1690,7 @@ static void select_and_update(Ctx& c, int B, const int* row_map) {
 
 static void run_step(Ctx& c, int B) {
   // one decode step: forward all rows at slot *slot, select, update (advances *slot)
-  Model& m = *c.m;
-  FwdArgs f;
-  f.rows = c.K * B;
-  f.Tn = 1;
-  f.rmul = 1;
-  f.tok = c.hist;
-  f.tok_ld = c.Tctx;
-  f.pad_seq = c.pad_row;
-  f.prefill = false;
-  f.anc = c.beam ? c.anc : nullptr;
+  const FwdArgs f = fwd_step(c, B);
   dec_step(c, f);
   dec_logits(c, nullptr, f.rows, true);
   debug_sync(c, "logits", -1);
@@ -1791,32 +1746,89 @@ static void ensure_prepared(Model& m) {
   m.dirty = false;
 }
 
-static ResultHolder* transcribe(Ctx& c, const float* pcm_dev, long stride, const long* lens, const int32_t* seek, int B,
-                                const int32_t* prompt_ids, const int32_t* prompt_lens) {
-  Model& m = *c.m;
-  WMX_CHECK(m.initialized, "transcribe: model weights not initialised");
-  ensure_prepared(m);
-  WMX_CHECK(B >= 1 && B <= c.maxB, "transcribe: batch exceeds max_batch");
-  const int K = c.K, R = K * B, V = m.d.n_vocab, T = c.Tctx;
-  const Special& sp = c.sp;
-  // per-call device words: the non-finite guard, and the fused MLP's slice counters + timeout word (zeroed every
-  // call, so the monotonic counters never approach 2^32 and a timeout fails only the call it happened in)
-  WMX_HIP(hipMemsetAsync(c.nf_err, 0, 4, c.st));
-  rec(c, 0);
-  logmel_dev(c, pcm_dev, stride, lens, seek, B, c.mel);
-  rec(c, 1);
-  encode(c, B);
-  debug_device("encode");
-  rec(c, 2);
-  cross_kv(c, B);
-  debug_device("cross_kv");
-  rec(c, 3);
+// ALGORITHMIC bytes of the decode step's launches over the K * B rows of B windows: weights + activations in +
+// activations out (16-bit), the cross K/V images (fp8 decode: weights and images at 1 byte per element; activations
+// stay 16-bit).  The one table behind the in-situ probe's figures (decode_loop) and wmx_ctx_bench_kernel's.
+struct StepBytes {
+  double qkv, proj, fc1, fc2;  // the projections: 3d x d, d x d, 4d x d, d x 4d
+  double cross;      // cross attention: images + q / o rows (+ the d x d query weights when it projects its queries)
+  double cross_qin;  // ... and the LN2 rows the fused projection reads (counted by the in-situ probe only)
+  double reduce_ln;  // reduce_ln after a d x d projection: its partials, x in and out, the 16-bit LN rows
+};
+static StepBytes step_bytes(const Ctx& c, int B) {
+  const Model& m = *c.m;
+  const int R = c.K * B, dt = m.d.n_text_state;
+  const double d = dt, r = R, ww = m.w8 ? 1.0 : 2.0, iw = m.kv8 ? 1.0 : 2.0;
+  auto proj = [&](double n, double k) { return n * k * ww + r * k * 2 + r * n * 2; };
+  StepBytes v;
+  v.qkv = proj(3 * d, d);
+  v.proj = proj(d, d);
+  v.fc1 = proj(4 * d, d);
+  v.fc2 = proj(d, 4 * d);
+  v.cross = (double)B * 1500 * 2 * d * iw + 2.0 * r * d * 2 + (c.xq_fused ? d * d * ww : 0.0);
+  v.cross_qin = c.xq_fused ? r * d * 2 : 0.0;
+  v.reduce_ln = (double)part_splits(R, dt, dt, c.part_elems) * r * d * 4 + 2.0 * r * d * 4 + r * d * 2;
+  return v;
+}
 
-  // ---- prompts (left padded to Pmax) ----
+// logits of decoder rows [0, rows_all) of c.dx, in chunks of c.logits_rows: after each chunk's final LN + logits GEMM
+// `each(r0, n)` issues what consumes c.logits, then the stream is synchronised (the chunk's host index vector)
+template <class F>
+static void logits_in_chunks(Ctx& c, int rows_all, F&& each) {
+  for (int r0 = 0; r0 < rows_all; r0 += c.logits_rows) {
+    const int n = std::min(c.logits_rows, rows_all - r0);
+    std::vector<int> g(n);
+    for (int i = 0; i < n; ++i) g[i] = r0 + i;
+    WMX_HIP(hipMemcpyAsync(c.gather, g.data(), n * 4, hipMemcpyHostToDevice, c.st));
+    dec_logits(c, c.gather, n);
+    each(r0, n);
+    sync(c);
+  }
+}
+
+// The decode rows' layout: window b's sequence left-padded to P in each of its K rows (pad_row / pad_win = the pad);
+// the slots below P live in the window's first cache row b * K, every later slot in the row's own (anc)
+struct RowLayout {
+  std::vector<int> hist, anc, pad_row, pad_win;
+};
+static RowLayout row_layout(const Ctx& c, int B, int P, const std::vector<std::vector<int>>& seqs) {
+  const int K = c.K, R = K * B, T = c.Tctx;
+  RowLayout y{std::vector<int>((size_t)R * T, 0), std::vector<int>((size_t)R * T, 0), std::vector<int>(R),
+              std::vector<int>(B)};
+  for (int b = 0; b < B; ++b) {
+    const int pad = P - (int)seqs[b].size();
+    y.pad_win[b] = pad;
+    for (int j = 0; j < K; ++j) {
+      const int r = b * K + j;
+      y.pad_row[r] = pad;
+      for (size_t i = 0; i < seqs[b].size(); ++i) y.hist[(size_t)r * T + pad + i] = seqs[b][i];
+      for (int s = 0; s < T; ++s) y.anc[(size_t)r * T + s] = s < P ? b * K : r;
+    }
+  }
+  return y;
+}
+
+// what the stages of one transcribe call hand on
+struct Call {
+  int B = 0;
+  bool detect = false;  // language detection (no language given)
+  int task_tok = 0;
+  int Pmax = 0;      // prompt length all windows are left-padded to
+  int sot_tail = 3;  // sot sits at Pmax - sot_tail
+  int max_new = 0, steps = 0;
+};
+
+// stage 3 -> 4: the prompts (left padded to Pmax), the rows' histories and ancestry, the row state reset
+static Call setup_rows(Ctx& c, int B, const int32_t* prompt_ids, const int32_t* prompt_lens) {
+  const int K = c.K, R = K * B, T = c.Tctx;
+  const Special& sp = c.sp;
+  Call q;
+  q.B = B;
+  q.detect = c.o.language < 0;
+  q.task_tok = c.o.task == WMX_TASK_TRANSLATE ? sp.translate : sp.transcribe;
+  q.sot_tail = c.o.without_timestamps ? 4 : 3;
+  const int lang_ph = q.detect ? sp.lang0 : c.o.language;
   std::vector<std::vector<int>> seqs(B);
-  const bool detect = c.o.language < 0;
-  const int lang_ph = detect ? sp.lang0 : c.o.language;
-  const int task_tok = c.o.task == WMX_TASK_TRANSLATE ? sp.translate : sp.transcribe;
   long poff = 0;
   for (int b = 0; b < B; ++b) {
     std::vector<int>& s = seqs[b];
@@ -1829,27 +1841,16 @@ static ResultHolder* transcribe(Ctx& c, const float* pcm_dev, long stride, const
     poff += pl;
     s.push_back(sp.sot);
     s.push_back(lang_ph);
-    s.push_back(task_tok);
+    s.push_back(q.task_tok);
     if (c.o.without_timestamps) s.push_back(sp.no_timestamps);
   }
-  int Pmax = 0;
-  for (auto& s : seqs) Pmax = std::max(Pmax, (int)s.size());
-  const int sot_tail = c.o.without_timestamps ? 4 : 3;  // sot sits at Pmax - sot_tail
-  std::vector<int> hist((size_t)R * T, 0), pad_row(R), pad_win(B), anc((size_t)R * T, 0), lslot(B, Pmax - sot_tail + 1);
-  for (int b = 0; b < B; ++b) {
-    const int pad = Pmax - (int)seqs[b].size();
-    pad_win[b] = pad;
-    for (int j = 0; j < K; ++j) {
-      const int r = b * K + j;
-      pad_row[r] = pad;
-      for (size_t i = 0; i < seqs[b].size(); ++i) hist[(size_t)r * T + pad + i] = seqs[b][i];
-      for (int s = 0; s < T; ++s) anc[(size_t)r * T + s] = s < Pmax ? b * K : r;
-    }
-  }
-  WMX_HIP(hipMemcpyAsync(c.hist, hist.data(), hist.size() * 4, hipMemcpyHostToDevice, c.st));
-  WMX_HIP(hipMemcpyAsync(c.anc, anc.data(), anc.size() * 4, hipMemcpyHostToDevice, c.st));
-  WMX_HIP(hipMemcpyAsync(c.pad_row, pad_row.data(), R * 4, hipMemcpyHostToDevice, c.st));
-  WMX_HIP(hipMemcpyAsync(c.pad_win, pad_win.data(), B * 4, hipMemcpyHostToDevice, c.st));
+  for (auto& s : seqs) q.Pmax = std::max(q.Pmax, (int)s.size());
+  const RowLayout y = row_layout(c, B, q.Pmax, seqs);
+  const std::vector<int> lslot(B, q.Pmax - q.sot_tail + 1);
+  WMX_HIP(hipMemcpyAsync(c.hist, y.hist.data(), y.hist.size() * 4, hipMemcpyHostToDevice, c.st));
+  WMX_HIP(hipMemcpyAsync(c.anc, y.anc.data(), y.anc.size() * 4, hipMemcpyHostToDevice, c.st));
+  WMX_HIP(hipMemcpyAsync(c.pad_row, y.pad_row.data(), R * 4, hipMemcpyHostToDevice, c.st));
+  WMX_HIP(hipMemcpyAsync(c.pad_win, y.pad_win.data(), B * 4, hipMemcpyHostToDevice, c.st));
   WMX_HIP(hipMemcpyAsync(c.lang_slot, lslot.data(), B * 4, hipMemcpyHostToDevice, c.st));
   // row state reset
   WMX_HIP(hipMemsetAsync(c.rp.ns, 0, R * 4, c.st));
@@ -1866,67 +1867,49 @@ static ResultHolder* transcribe(Ctx& c, const float* pcm_dev, long stride, const
   WMX_HIP(hipMemcpyAsync(c.row_map, rmap.data(), R * 4, hipMemcpyHostToDevice, c.st));
   debug_device("prompt setup");
   sync(c);
+  return q;
+}
 
-  // ---- language detection: one decoder step on <|startoftranscript|> ----
-  std::vector<int> lang_out(B, c.o.language);
-  std::vector<float> lang_p(B, 1.0f);
-  if (detect) {
-    // a temporary token row per window: hist_tmp[b*K][0] = sot
-    std::vector<int> t1((size_t)B * K * T, sp.sot);
-    WMX_HIP(hipMemcpyAsync(c.hist_tmp, t1.data(), t1.size() * 4, hipMemcpyHostToDevice, c.st));
-    set_slot(c, 0);
-    FwdArgs f;
-    f.rows = B;
-    f.Tn = 1;
-    f.rmul = K;
-    f.tok = c.hist_tmp;
-    f.tok_ld = (long)K * T;
-    f.pad_seq = nullptr;
-    f.prefill = true;
-    f.anc = nullptr;
-    // the split-K decode step, one row per window (it writes cache slot 0 of rows 0 .. B-1, which the prompt
-    // prefill rewrites or no hypothesis reads) instead of dec_forward's unsplit projections
-    f.win_rows = 1;
-    dec_step_fast(c, f);
-    dec_logits(c, nullptr, B, true);
-    launch_lang_detect(c.logits, c.ldl, sp.lang0, sp.n_langs, B, K, c.hist, T, c.lang_slot, c.lang_tok, c.lang_prob, c.st,
-                       c.nf_err);
-    debug_sync(c, "lang_detect", -1);
-  }
-  rec(c, 4);
-
-  // ---- prompt prefill ----
+// ... language detection: one decoder step on <|startoftranscript|>, its token written into the rows' histories
+static void detect_language(Ctx& c, const Call& q) {
+  const int B = q.B, K = c.K, T = c.Tctx;
+  // a temporary token row per window: hist_tmp[b*K][0] = sot
+  std::vector<int> t1((size_t)B * K * T, c.sp.sot);
+  WMX_HIP(hipMemcpyAsync(c.hist_tmp, t1.data(), t1.size() * 4, hipMemcpyHostToDevice, c.st));
   set_slot(c, 0);
-  {
-    FwdArgs f;
-    f.rows = B;
-    f.Tn = Pmax;
-    f.rmul = K;
-    f.tok = c.hist;
-    f.tok_ld = (long)K * T;
-    f.pad_seq = c.pad_win;
-    f.prefill = true;
-    f.anc = nullptr;
-    dec_forward(c, f);
-    std::vector<int> g(2 * B);
-    for (int b = 0; b < B; ++b) {
-      g[b] = b * Pmax + Pmax - 1;
-      g[B + b] = b * Pmax + Pmax - sot_tail;
-    }
-    WMX_HIP(hipMemcpyAsync(c.gather, g.data(), g.size() * 4, hipMemcpyHostToDevice, c.st));
-    dec_logits(c, c.gather, 2 * B);
-    launch_token_prob(c.logits + (size_t)B * c.ldl, c.ldl, V, sp.no_speech, B, c.nospeech, c.st);
-    sync(c);
+  // the split-K decode step in its fast form, one row per window (it writes cache slot 0 of rows 0 .. B-1, which the
+  // prompt prefill rewrites or no hypothesis reads) instead of dec_forward's unsplit projections
+  FwdArgs f = fwd_prefill(c, B, 1, c.hist_tmp, nullptr);
+  f.win_rows = 1;
+  dec_step_as(c, f, false);
+  dec_logits(c, nullptr, B, true);
+  launch_lang_detect(c.logits, c.ldl, c.sp.lang0, c.sp.n_langs, B, K, c.hist, T, c.lang_slot, c.lang_tok, c.lang_prob,
+                     c.st, c.nf_err);
+  debug_sync(c, "lang_detect", -1);
+}
+
+// stage 4 -> 5: the prompt prefill (logits of the last prompt position and of sot: the no-speech probability) and the
+// first selection from the prefill logits (rows of a window share their window's logits row)
+static void prefill_and_select(Ctx& c, Call& q) {
+  const int B = q.B, R = c.K * B, T = c.Tctx, Pmax = q.Pmax;
+  set_slot(c, 0);
+  dec_forward(c, fwd_prefill(c, B, Pmax, c.hist, c.pad_win));
+  std::vector<int> g(2 * B);
+  for (int b = 0; b < B; ++b) {
+    g[b] = b * Pmax + Pmax - 1;
+    g[B + b] = b * Pmax + Pmax - q.sot_tail;
   }
+  WMX_HIP(hipMemcpyAsync(c.gather, g.data(), g.size() * 4, hipMemcpyHostToDevice, c.st));
+  dec_logits(c, c.gather, 2 * B);
+  launch_token_prob(c.logits + (size_t)B * c.ldl, c.ldl, c.m->d.n_vocab, c.sp.no_speech, B, c.nospeech, c.st);
+  sync(c);
   // this call's sampling seed (slot word 2, read by the captured selection launches)
   if (c.sampling) {
     c.pinned_i[3] = (int)c.o.sample_seed;
     WMX_HIP(hipMemcpyAsync(c.slot + 2, c.pinned_i + 3, 4, hipMemcpyHostToDevice, c.st));
   }
-  // first selection from the prefill logits (rows of a window share their window's logits row)
-  const int max_new = std::max(0, std::min(c.o.max_new_tokens, T - Pmax));
+  q.max_new = std::max(0, std::min(c.o.max_new_tokens, T - Pmax));
   set_slot(c, Pmax - 1);
-  int steps = 0;
   if (c.rec_logits) {  // recorder step 0 = this first selection (slot Pmax - 1)
     c.rec_R = R;
     c.pinned_i[1] = Pmax - 1;
@@ -1934,29 +1917,33 @@ static ResultHolder* transcribe(Ctx& c, const float* pcm_dev, long stride, const
     WMX_HIP(hipMemsetD32Async((hipDeviceptr_t)c.rec_sel, -1, (size_t)c.rec_cap * c.R * 2, c.st));
     sync(c);
   }
-  if (max_new > 0) {
+  if (q.max_new > 0) {
     select_and_update(c, B, c.row_map);
     debug_sync(c, "first_select", -1);
-    steps = 1;
+    q.steps = 1;
   }
-  rec(c, 5);
-  // ---- decode loop: one hipGraph replay per step ----
+}
+
+// stage 5 -> 6: the decode loop, one hipGraph replay per step (a chunk of kGraphChunk steps per launch), n_done read
+// back between chunks; with a lockstep group, its start barrier and chunk barriers
+static void decode_loop(Ctx& c, Call& q) {
+  const int B = q.B, R = c.K * B, T = c.Tctx, max_new = q.max_new;
+  int& steps = q.steps;
   const int need_done = c.beam ? B : R;
-  c.probe_slots[0] = steps > 0 ? Pmax : 0;  // slots of the graph-replayed steps of this call
+  c.probe_slots[0] = steps > 0 ? q.Pmax : 0;  // slots of the graph-replayed steps of this call
 
   if (c.probe_kernel >= 0) {  // per-workgroup records of this call only (read after the timed region)
     WMX_HIP(hipMemsetAsync(c.probe_buf, 0, (size_t)kProbeLaunches * T * kProbeWG * 2 * 8, c.st));
   }
-  {  // ALGORITHMIC bytes of one launch: weights + activations in + activations out (16-bit), cross K/V
-     // (fp8 decode: weights and cross K/V images at 1 byte per element; activations stay 16-bit)
-    const double d = m.d.n_text_state, w2 = 2.0, r = R, ww = m.w8 ? 1.0 : 2.0, iw = m.kv8 ? 1.0 : 2.0;
-    auto proj = [&](double n, double k) { return n * k * ww + r * k * w2 + r * n * w2; };
-    // (fused cross-q: the cross attention also streams the d x d query weights and reads the LN2 rows)
-    const bool xqf = c.xq_fused;
-    const double xq = xqf ? d * d * ww + r * d * w2 : 0.0;
-    const double v[kProbeLaunches] = {proj(3 * d, d), proj(d, d), xqf ? 0.0 : proj(d, d), proj(d, d),
-                                      proj(4 * d, d), proj(d, 4 * d), (double)B * 1500 * 2 * d * iw + 2.0 * r * d * w2 + xq};
-    for (int k = 0; k < kProbeLaunches; ++k) c.probe_bytes[k] = v[k];
+  {  // the probed launches' algorithmic bytes (fused cross-q: no cross-q launch)
+    const StepBytes v = step_bytes(c, B);
+    for (double& p : c.probe_bytes) p = 0;
+    c.probe_bytes[kProbeQKV] = v.qkv;
+    c.probe_bytes[kProbeOut] = c.probe_bytes[kProbeCrossOut] = v.proj;
+    c.probe_bytes[kProbeCrossQ] = c.xq_fused ? 0.0 : v.proj;
+    c.probe_bytes[kProbeFc1] = v.fc1;
+    c.probe_bytes[kProbeFc2] = v.fc2;
+    c.probe_bytes[kProbeCross] = v.cross + v.cross_qin;
   }
   if (c.o.use_graph && steps < max_new) ensure_step_graphs(c, B);
   if (c.lockstep && steps < max_new) {  // idle stream, then the group's barrier: the step graphs start together
@@ -1996,39 +1983,49 @@ static ResultHolder* transcribe(Ctx& c, const float* pcm_dev, long stride, const
 
     if (c.pinned_i[0] >= need_done) break;
   }
-  // this member's decode loop is over: release the partners' chunk barriers now, not when transcribe returns
-  // (the read-back, the alignment forward and the host DTW below would otherwise hold them at the timeout)
-  if (lk_leave.p) {
-    lk_leave.p->leave();
-    lk_leave.p = nullptr;
-  }
+  // this member's decode loop is over: the guard releases the partners' chunk barriers here, not when transcribe
+  // returns (the read-back, the alignment forward and the host DTW would otherwise hold them at the timeout)
   c.last_steps = steps;
-  rec(c, 6);
-  c.probe_slots[1] = Pmax - 1 + steps;
+}
 
-  // ---- read back and finalise (openai BeamSearchDecoder.finalize + MaximumLikelihoodRanker) ----
-  std::vector<int> h((size_t)R * T), ns(R), done(R);
-  std::vector<float> slp(R), nosp(B);
+// the search state of one call on the host: histories, per-row counts and log-probabilities, per-window no-speech and
+// language, and (beam search) the finished hypotheses
+struct Readback {
+  std::vector<int> h, ns, done, lang, fcount, flen, fh;
+  std::vector<float> slp, nosp, lang_p, fscore;
+};
+
+static Readback read_back(Ctx& c, const Call& q) {
+  const int B = q.B, K = c.K, R = K * B, T = c.Tctx, Pmax = q.Pmax;
+  Readback rb;
+  rb.h.resize((size_t)R * T);
+  rb.ns.resize(R);
+  rb.done.resize(R);
+  rb.slp.resize(R);
+  rb.nosp.resize(B);
+  rb.lang.assign(B, c.o.language);
+  rb.lang_p.assign(B, 1.0f);
   int nf_err = 0;
   WMX_HIP(hipMemcpyAsync(&nf_err, c.nf_err, 4, hipMemcpyDeviceToHost, c.st));
-  WMX_HIP(hipMemcpyAsync(h.data(), c.hist, h.size() * 4, hipMemcpyDeviceToHost, c.st));
-  WMX_HIP(hipMemcpyAsync(ns.data(), c.rp.ns, R * 4, hipMemcpyDeviceToHost, c.st));
-  WMX_HIP(hipMemcpyAsync(done.data(), c.rp.done, R * 4, hipMemcpyDeviceToHost, c.st));
-  WMX_HIP(hipMemcpyAsync(slp.data(), c.rp.sum_lp, R * 4, hipMemcpyDeviceToHost, c.st));
-  WMX_HIP(hipMemcpyAsync(nosp.data(), c.nospeech, B * 4, hipMemcpyDeviceToHost, c.st));
-  if (detect) {
-    WMX_HIP(hipMemcpyAsync(lang_out.data(), c.lang_tok, B * 4, hipMemcpyDeviceToHost, c.st));
-    WMX_HIP(hipMemcpyAsync(lang_p.data(), c.lang_prob, B * 4, hipMemcpyDeviceToHost, c.st));
+  WMX_HIP(hipMemcpyAsync(rb.h.data(), c.hist, rb.h.size() * 4, hipMemcpyDeviceToHost, c.st));
+  WMX_HIP(hipMemcpyAsync(rb.ns.data(), c.rp.ns, R * 4, hipMemcpyDeviceToHost, c.st));
+  WMX_HIP(hipMemcpyAsync(rb.done.data(), c.rp.done, R * 4, hipMemcpyDeviceToHost, c.st));
+  WMX_HIP(hipMemcpyAsync(rb.slp.data(), c.rp.sum_lp, R * 4, hipMemcpyDeviceToHost, c.st));
+  WMX_HIP(hipMemcpyAsync(rb.nosp.data(), c.nospeech, B * 4, hipMemcpyDeviceToHost, c.st));
+  if (q.detect) {
+    WMX_HIP(hipMemcpyAsync(rb.lang.data(), c.lang_tok, B * 4, hipMemcpyDeviceToHost, c.st));
+    WMX_HIP(hipMemcpyAsync(rb.lang_p.data(), c.lang_prob, B * 4, hipMemcpyDeviceToHost, c.st));
   }
   const int nfin = B * c.max_cand;
-  std::vector<int> fcount(B), flen(nfin), fh;
-  std::vector<float> fscore(nfin);
+  rb.fcount.resize(B);
+  rb.flen.resize(nfin);
+  rb.fscore.resize(nfin);
   if (c.beam) {
-    fh.resize((size_t)nfin * T);
-    WMX_HIP(hipMemcpyAsync(fcount.data(), c.bs.fin_count, B * 4, hipMemcpyDeviceToHost, c.st));
-    WMX_HIP(hipMemcpyAsync(flen.data(), c.bs.fin_len, nfin * 4, hipMemcpyDeviceToHost, c.st));
-    WMX_HIP(hipMemcpyAsync(fscore.data(), c.bs.fin_score, nfin * 4, hipMemcpyDeviceToHost, c.st));
-    WMX_HIP(hipMemcpyAsync(fh.data(), c.bs.fin_hist, fh.size() * 4, hipMemcpyDeviceToHost, c.st));
+    rb.fh.resize((size_t)nfin * T);
+    WMX_HIP(hipMemcpyAsync(rb.fcount.data(), c.bs.fin_count, B * 4, hipMemcpyDeviceToHost, c.st));
+    WMX_HIP(hipMemcpyAsync(rb.flen.data(), c.bs.fin_len, nfin * 4, hipMemcpyDeviceToHost, c.st));
+    WMX_HIP(hipMemcpyAsync(rb.fscore.data(), c.bs.fin_score, nfin * 4, hipMemcpyDeviceToHost, c.st));
+    WMX_HIP(hipMemcpyAsync(rb.fh.data(), c.bs.fin_hist, rb.fh.size() * 4, hipMemcpyDeviceToHost, c.st));
   }
   sync(c);
   if (nf_err < 0)
@@ -2039,181 +2036,195 @@ static ResultHolder* transcribe(Ctx& c, const float* pcm_dev, long stride, const
                                      " (slot " + std::to_string(slot) + "), row " + std::to_string(row) +
                                      " (window " + std::to_string(row / K) + ")");
   }
-  auto* res = new ResultHolder();
-  res->data.resize(B);
-  res->win.resize(B);
-  std::vector<float> sum_lp(B);
-  for (int b = 0; b < B; ++b) {
-    std::vector<int>& toks = res->data[b].tokens;
-    if (K == 1) {
-      for (int i = 0; i < ns[b]; ++i) toks.push_back(h[(size_t)b * T + Pmax + i]);
-      sum_lp[b] = slp[b];
-    } else if (c.sampling) {
-      // best_of sampled rows: the highest sum_logprob / length (CT2 sorts its num_hypotheses by that score and
-      // faster-whisper takes sequences_ids[0]); ties keep the lower row
-      int best = 0;
-      double best_score = -INFINITY;
-      for (int j = 0; j < K; ++j) {
-        const int r = b * K + j;
-        const double L = std::max(ns[r], 1);
-        const double pen = c.o.length_penalty == 1.0f ? L : std::pow((5.0 + L) / 6.0, (double)c.o.length_penalty);
-        const double sc = slp[r] / pen;
-        if (sc > best_score) {
-          best = j;
-          best_score = sc;
-        }
-      }
-      const int r = b * K + best;
-      for (int i = 0; i < ns[r]; ++i) toks.push_back(h[(size_t)r * T + Pmax + i]);
-      sum_lp[b] = slp[r];
-    } else {
-      struct Cand {
-        std::vector<int> t;
-        float s;
-      };
-      std::vector<Cand> fin;
-      for (int f = 0; f < fcount[b]; ++f) {
-        const int idx = b * c.max_cand + f;
-        Cand cd;
-        for (int s = Pmax; s < flen[idx]; ++s) cd.t.push_back(fh[(size_t)idx * T + s]);
-        cd.s = fscore[idx];
-        fin.push_back(cd);
-      }
-      if ((int)fin.size() < K) {
-        std::vector<int> order(K);
-        for (int j = 0; j < K; ++j) order[j] = j;
-        std::stable_sort(order.begin(), order.end(),
-                         [&](int a, int bb) { return slp[b * K + a] > slp[b * K + bb]; });
-        for (int j : order) {
-          const int r = b * K + j;
-          Cand cd;
-          for (int i = 0; i < ns[r]; ++i) cd.t.push_back(h[(size_t)r * T + Pmax + i]);
-          cd.s = slp[r];
-          bool dup = false;
-          for (auto& e : fin) dup = dup || e.t == cd.t;
-          if (!dup) fin.push_back(cd);
-          if ((int)fin.size() >= K) break;
-        }
-      }
-      int best = -1;
-      double best_score = -INFINITY;
-      for (size_t i = 0; i < fin.size(); ++i) {
-        const double L = std::max<size_t>(fin[i].t.size(), 1);
-        const double pen = c.o.length_penalty == 1.0f ? L : std::pow((5.0 + L) / 6.0, (double)c.o.length_penalty);
-        const double sc = fin[i].s / pen;
-        if (best < 0 || sc > best_score) {
-          best = (int)i;
-          best_score = sc;
-        }
-      }
-      if (best >= 0) {
-        toks = fin[best].t;
-        sum_lp[b] = fin[best].s;
+  return rb;
+}
+
+// a hypothesis' score: sum_logprob over its length, or over ((5 + length) / 6) ^ length_penalty
+static double length_normalised(double sum_lp, size_t len, float length_penalty) {
+  const double L = (double)std::max<size_t>(len, 1);
+  return sum_lp / (length_penalty == 1.0f ? L : std::pow((5.0 + L) / 6.0, (double)length_penalty));
+}
+
+// Window b's hypothesis, a pure function of the read-back arrays (K rows per window of T slots, the new tokens from
+// slot Pmax): the greedy row; of best_of sampled rows the highest sum_logprob / length (CT2 sorts its num_hypotheses
+// by that score and faster-whisper takes sequences_ids[0]; ties keep the lower row); of a beam search the finished
+// hypotheses, filled up to K with the live rows by sum_logprob, ranked by the length-normalised score (openai
+// BeamSearchDecoder.finalize + MaximumLikelihoodRanker)
+struct Hypothesis {
+  std::vector<int> tokens;
+  float sum_lp = 0.f;
+};
+static Hypothesis choose_hypothesis(const Readback& rb, int b, int K, int T, int Pmax, int max_cand, bool sampling,
+                                    float length_penalty) {
+  auto row = [&](int r) {
+    Hypothesis y;
+    for (int i = 0; i < rb.ns[r]; ++i) y.tokens.push_back(rb.h[(size_t)r * T + Pmax + i]);
+    y.sum_lp = rb.slp[r];
+    return y;
+  };
+  if (K == 1) return row(b);
+  std::vector<Hypothesis> cand;
+  if (sampling) {
+    for (int j = 0; j < K; ++j) cand.push_back(row(b * K + j));
+  } else {
+    for (int f = 0; f < rb.fcount[b]; ++f) {
+      const int idx = b * max_cand + f;
+      Hypothesis y;
+      for (int s = Pmax; s < rb.flen[idx]; ++s) y.tokens.push_back(rb.fh[(size_t)idx * T + s]);
+      y.sum_lp = rb.fscore[idx];
+      cand.push_back(y);
+    }
+    if ((int)cand.size() < K) {
+      std::vector<int> order(K);
+      for (int j = 0; j < K; ++j) order[j] = j;
+      std::stable_sort(order.begin(), order.end(),
+                       [&](int a, int bb) { return rb.slp[b * K + a] > rb.slp[b * K + bb]; });
+      for (int j : order) {
+        const Hypothesis y = row(b * K + j);
+        bool dup = false;
+        for (auto& e : cand) dup = dup || e.tokens == y.tokens;
+        if (!dup) cand.push_back(y);
+        if ((int)cand.size() >= K) break;
       }
     }
+  }
+  int best = -1;
+  double best_score = -INFINITY;
+  for (size_t i = 0; i < cand.size(); ++i) {
+    const double sc = length_normalised(cand[i].sum_lp, cand[i].tokens.size(), length_penalty);
+    if (best < 0 || sc > best_score) {
+      best = (int)i;
+      best_score = sc;
+    }
+  }
+  return best >= 0 ? cand[best] : Hypothesis{};
+}
+
+// stage 6 -> 7: word alignment: forward sot + text + eot, alignment-head attention -> matrix -> DTW on host threads
+static void align_words(Ctx& c, const Call& q, ResultHolder& res) {
+  const int B = q.B, K = c.K, T = c.Tctx;
+  const Special& sp = c.sp;
+  std::vector<std::vector<int>> rows(B);
+  std::vector<int> ntext(B);
+  int Tn = 0;
+  for (int b = 0; b < B; ++b) {
+    std::vector<int>& s = rows[b];
+    // openai timing.find_alignment: sot_sequence + <|notimestamps|> + text tokens + eot
+    s = {sp.sot, res.win[b].language, q.task_tok, sp.no_timestamps};
+    for (int t : res.data[b].tokens)
+      if (t < sp.eot) s.push_back(t);
+    ntext[b] = (int)s.size() - 4;
+    s.push_back(sp.eot);
+    Tn = std::max(Tn, (int)s.size());
+  }
+  WMX_CHECK(Tn <= T, "alignment: sequence too long");
+  std::vector<int> tok((size_t)B * K * T, 0), ntok(B), nframes(B), target((size_t)B * Tn, -1);
+  for (int b = 0; b < B; ++b) {
+    for (size_t i = 0; i < rows[b].size(); ++i) tok[(size_t)b * K * T + i] = rows[b][i];
+    ntok[b] = (int)rows[b].size();
+    nframes[b] = res.win[b].seek_frames;
+    for (int i = 0; i < ntext[b]; ++i) target[(size_t)b * Tn + 3 + i] = rows[b][4 + i];
+  }
+  WMX_HIP(hipMemcpyAsync(c.hist_tmp, tok.data(), tok.size() * 4, hipMemcpyHostToDevice, c.st));
+  WMX_HIP(hipMemcpyAsync(c.a_ntok, ntok.data(), B * 4, hipMemcpyHostToDevice, c.st));
+  WMX_HIP(hipMemcpyAsync(c.a_nframes, nframes.data(), B * 4, hipMemcpyHostToDevice, c.st));
+  WMX_HIP(hipMemcpyAsync(c.a_target, target.data(), target.size() * 4, hipMemcpyHostToDevice, c.st));
+  set_slot(c, 0);
+  launch_align_matrix_zero(c.align_out, B, Tn, 1500, c.st);
+  FwdArgs f = fwd_prefill(c, B, Tn, c.hist_tmp, nullptr);
+  f.align = true;
+  dec_forward(c, f);
+  const int nh_total = (int)c.align_heads.size() / 2;
+  launch_align_matrix_scale(c.align_out, B, Tn, 1500, c.a_ntok, c.a_nframes, 1.0f / nh_total, c.st);
+  // text-token probabilities from the logits of every position
+  logits_in_chunks(c, B * Tn, [&](int r0, int n) {
+    launch_text_prob(c.logits, c.ldl, sp.eot, c.a_target + r0, n, c.tprob + r0, c.st);
+  });
+  c.last_align_ok = false;
+  if (!c.h_align) {
+    WMX_HIP(hipHostMalloc(&c.h_align, (size_t)c.maxB * c.Tctx * 1500 * sizeof(float)));
+    WMX_HIP(hipHostMalloc(&c.h_tp, (size_t)c.maxB * c.Tctx * sizeof(float)));
+  }
+  float* const mat = c.h_align;  // [B][Tn][1500], pinned
+  float* const tp = c.h_tp;
+  WMX_HIP(hipMemcpyAsync(mat, c.align_out, (size_t)B * Tn * 1500 * 4, hipMemcpyDeviceToHost, c.st));
+  WMX_HIP(hipMemcpyAsync(tp, c.tprob, (size_t)B * Tn * 4, hipMemcpyDeviceToHost, c.st));
+  sync(c);
+  // DTW per window on host threads
+  std::vector<std::thread> th;
+  std::atomic<int> next{0};
+  const int nth = std::min<int>(B, std::max(1u, std::min(16u, std::thread::hardware_concurrency())));
+  for (int t = 0; t < nth; ++t)
+    th.emplace_back([&]() {
+      std::vector<int> ti, tj;
+      for (int b = next++; b < B; b = next++) {
+        WindowOut& wo = res.data[b];
+        const int n = ntext[b] + 1, nf = nframes[b] / 2;
+        wo.probs.assign(tp + (size_t)b * Tn + 3, tp + (size_t)b * Tn + 3 + ntext[b]);
+        if (nf <= 0) {
+          wo.jump_times.assign(n, 0.f);
+          continue;
+        }
+        dtw(mat + ((size_t)b * Tn + 3) * 1500, n, nf, 1500, ti, tj);
+        wo.jump_times.clear();
+        for (size_t k = 0; k < ti.size(); ++k)
+          if (k == 0 || ti[k] != ti[k - 1]) wo.jump_times.push_back(tj[k] / 50.0f);
+        wo.jump_times.resize(n, wo.jump_times.empty() ? 0.f : wo.jump_times.back());
+      }
+    });
+  for (auto& x : th) x.join();
+  c.last_align_ok = true;  // h_align is read by wmx_ctx_alignment_matrix until the next transcribe
+  c.last_ntext = ntext;
+  c.last_nframes = nframes;
+  c.last_align_Tn = Tn;
+}
+
+// the stages of one call, each between two of the events behind stage_ms: log-mel, encoder, cross K/V, row setup +
+// language detection, prefill + first selection, decode loop, read-back + hypothesis choice + word alignment
+static ResultHolder* transcribe(Ctx& c, const float* pcm_dev, long stride, const long* lens, const int32_t* seek, int B,
+                                const int32_t* prompt_ids, const int32_t* prompt_lens) {
+  Model& m = *c.m;
+  WMX_CHECK(m.initialized, "transcribe: model weights not initialised");
+  ensure_prepared(m);
+  WMX_CHECK(B >= 1 && B <= c.maxB, "transcribe: batch exceeds max_batch");
+  // per-call device word: the non-finite guard
+  WMX_HIP(hipMemsetAsync(c.nf_err, 0, 4, c.st));
+  rec(c, 0);
+  logmel_dev(c, pcm_dev, stride, lens, seek, B, c.mel);
+  rec(c, 1);
+  encode(c, B);
+  debug_device("encode");
+  rec(c, 2);
+  cross_kv(c, B);
+  debug_device("cross_kv");
+  rec(c, 3);
+  Call q = setup_rows(c, B, prompt_ids, prompt_lens);
+  if (q.detect) detect_language(c, q);
+  rec(c, 4);
+  prefill_and_select(c, q);
+  rec(c, 5);
+  decode_loop(c, q);
+  rec(c, 6);
+  c.probe_slots[1] = q.Pmax - 1 + q.steps;
+  const Readback rb = read_back(c, q);
+  std::unique_ptr<ResultHolder> res(new ResultHolder());
+  res->data.resize(B);
+  res->win.resize(B);
+  for (int b = 0; b < B; ++b) {
+    const Hypothesis y = choose_hypothesis(rb, b, c.K, c.Tctx, q.Pmax, c.max_cand, c.sampling, c.o.length_penalty);
+    res->data[b].tokens = y.tokens;
     wmx_window_result& w = res->win[b];
-    w.language = lang_out[b];
-    w.language_prob = lang_p[b];
-    w.n_tokens = (int)toks.size();
-    w.sum_logprob = sum_lp[b];
-    w.avg_logprob = sum_lp[b] / (toks.size() + 1);
-    w.no_speech_prob = nosp[b];
+    w.language = rb.lang[b];
+    w.language_prob = rb.lang_p[b];
+    w.n_tokens = (int)y.tokens.size();
+    w.sum_logprob = y.sum_lp;
+    w.avg_logprob = y.sum_lp / (y.tokens.size() + 1);
+    w.no_speech_prob = rb.nosp[b];
     const int F = (int)(lens[b] / 160) + 1;
     const int sk = seek ? seek[b] : 0;
     w.seek_frames = std::max(0, std::min(3000, F - 1 - sk));
   }
-
-  // ---- word alignment: forward sot + text + eot, alignment-head attention -> matrix -> DTW ----
-  if (c.o.word_timestamps) {
-    std::vector<std::vector<int>> rows(B);
-    std::vector<int> ntext(B);
-    int Tn = 0;
-    for (int b = 0; b < B; ++b) {
-      std::vector<int>& s = rows[b];
-      // openai timing.find_alignment: sot_sequence + <|notimestamps|> + text tokens + eot
-      s = {sp.sot, res->win[b].language, task_tok, sp.no_timestamps};
-      for (int t : res->data[b].tokens)
-        if (t < sp.eot) s.push_back(t);
-      ntext[b] = (int)s.size() - 4;
-      s.push_back(sp.eot);
-      Tn = std::max(Tn, (int)s.size());
-    }
-    WMX_CHECK(Tn <= T, "alignment: sequence too long");
-    std::vector<int> tok((size_t)B * K * T, 0), ntok(B), nframes(B), target((size_t)B * Tn, -1);
-    for (int b = 0; b < B; ++b) {
-      for (size_t i = 0; i < rows[b].size(); ++i) tok[(size_t)b * K * T + i] = rows[b][i];
-      ntok[b] = (int)rows[b].size();
-      nframes[b] = res->win[b].seek_frames;
-      for (int i = 0; i < ntext[b]; ++i) target[(size_t)b * Tn + 3 + i] = rows[b][4 + i];
-    }
-    WMX_HIP(hipMemcpyAsync(c.hist_tmp, tok.data(), tok.size() * 4, hipMemcpyHostToDevice, c.st));
-    WMX_HIP(hipMemcpyAsync(c.a_ntok, ntok.data(), B * 4, hipMemcpyHostToDevice, c.st));
-    WMX_HIP(hipMemcpyAsync(c.a_nframes, nframes.data(), B * 4, hipMemcpyHostToDevice, c.st));
-    WMX_HIP(hipMemcpyAsync(c.a_target, target.data(), target.size() * 4, hipMemcpyHostToDevice, c.st));
-    set_slot(c, 0);
-    launch_align_matrix_zero(c.align_out, B, Tn, 1500, c.st);
-    FwdArgs f;
-    f.rows = B;
-    f.Tn = Tn;
-    f.rmul = K;
-    f.tok = c.hist_tmp;
-    f.tok_ld = (long)K * T;
-    f.pad_seq = nullptr;
-    f.prefill = true;
-    f.anc = nullptr;
-    f.align = true;
-    dec_forward(c, f);
-    const int nh_total = (int)c.align_heads.size() / 2;
-    launch_align_matrix_scale(c.align_out, B, Tn, 1500, c.a_ntok, c.a_nframes, 1.0f / nh_total, c.st);
-    // text-token probabilities: logits of every position, in chunks of logits_rows
-    const int rows_all = B * Tn;
-    for (int r0 = 0; r0 < rows_all; r0 += c.logits_rows) {
-      const int n = std::min(c.logits_rows, rows_all - r0);
-      std::vector<int> g(n);
-      for (int i = 0; i < n; ++i) g[i] = r0 + i;
-      WMX_HIP(hipMemcpyAsync(c.gather, g.data(), n * 4, hipMemcpyHostToDevice, c.st));
-      dec_logits(c, c.gather, n);
-      launch_text_prob(c.logits, c.ldl, sp.eot, c.a_target + r0, n, c.tprob + r0, c.st);
-      sync(c);
-    }
-    c.last_align_ok = false;
-    if (!c.h_align) {
-      WMX_HIP(hipHostMalloc(&c.h_align, (size_t)c.maxB * c.Tctx * 1500 * sizeof(float)));
-      WMX_HIP(hipHostMalloc(&c.h_tp, (size_t)c.maxB * c.Tctx * sizeof(float)));
-    }
-    float* const mat = c.h_align;  // [B][Tn][1500], pinned
-    float* const tp = c.h_tp;
-    WMX_HIP(hipMemcpyAsync(mat, c.align_out, (size_t)B * Tn * 1500 * 4, hipMemcpyDeviceToHost, c.st));
-    WMX_HIP(hipMemcpyAsync(tp, c.tprob, (size_t)B * Tn * 4, hipMemcpyDeviceToHost, c.st));
-    sync(c);
-    // DTW per window on host threads
-    std::vector<std::thread> th;
-    std::atomic<int> next{0};
-    const int nth = std::min<int>(B, std::max(1u, std::min(16u, std::thread::hardware_concurrency())));
-    for (int t = 0; t < nth; ++t)
-      th.emplace_back([&]() {
-        std::vector<int> ti, tj;
-        for (int b = next++; b < B; b = next++) {
-          WindowOut& wo = res->data[b];
-          const int n = ntext[b] + 1, nf = nframes[b] / 2;
-          wo.probs.assign(tp + (size_t)b * Tn + 3, tp + (size_t)b * Tn + 3 + ntext[b]);
-          if (nf <= 0) {
-            wo.jump_times.assign(n, 0.f);
-            continue;
-          }
-          dtw(mat + ((size_t)b * Tn + 3) * 1500, n, nf, 1500, ti, tj);
-          wo.jump_times.clear();
-          for (size_t k = 0; k < ti.size(); ++k)
-            if (k == 0 || ti[k] != ti[k - 1]) wo.jump_times.push_back(tj[k] / 50.0f);
-          wo.jump_times.resize(n, wo.jump_times.empty() ? 0.f : wo.jump_times.back());
-        }
-      });
-    for (auto& x : th) x.join();
-    c.last_align_ok = true;  // h_align is read by wmx_ctx_alignment_matrix until the next transcribe
-    c.last_ntext = ntext;
-    c.last_nframes = nframes;
-    c.last_align_Tn = Tn;
-  }
+  if (c.o.word_timestamps) align_words(c, q, *res);
   rec(c, 7);
   WMX_HIP(hipEventSynchronize(c.ev[7]));
   for (int i = 0; i < 7; ++i) WMX_HIP(hipEventElapsedTime(&c.stage_ms[i], c.ev[i], c.ev[i + 1]));
@@ -2223,13 +2234,13 @@ static ResultHolder* transcribe(Ctx& c, const float* pcm_dev, long stride, const
     WindowOut& wo = res->data[b];
     w.tokens = wo.tokens.data();
     w.n_text_tokens = 0;
-    for (int t : wo.tokens) w.n_text_tokens += t < sp.eot;
+    for (int t : wo.tokens) w.n_text_tokens += t < c.sp.eot;
     w.jump_times = wo.jump_times.empty() ? nullptr : wo.jump_times.data();
     w.text_token_probs = wo.probs.empty() ? nullptr : wo.probs.data();
   }
   res->r.n_windows = B;
   res->r.windows = res->win.data();
-  return res;
+  return res.release();
 }
 
 }  // namespace wmx
@@ -2715,27 +2726,11 @@ wmx_status wmx_decoder_logits(wmx_ctx* x, const int32_t* tokens, const int32_t* 
       for (int i = 0; i < T; ++i) tok[(size_t)b * K * Tc + i] = tokens[(size_t)b * T + i];
     WMX_HIP(hipMemcpyAsync(c.hist_tmp, tok.data(), tok.size() * 4, hipMemcpyHostToDevice, c.st));
     set_slot(c, 0);
-    FwdArgs f;
-    f.rows = B;
-    f.Tn = T;
-    f.rmul = K;
-    f.tok = c.hist_tmp;
-    f.tok_ld = (long)K * Tc;
-    f.pad_seq = nullptr;
-    f.prefill = true;
-    f.anc = nullptr;
-    dec_forward(c, f);
-    const int rows_all = B * T;
-    for (int r0 = 0; r0 < rows_all; r0 += c.logits_rows) {
-      const int n = std::min(c.logits_rows, rows_all - r0);
-      std::vector<int> g(n);
-      for (int i = 0; i < n; ++i) g[i] = r0 + i;
-      WMX_HIP(hipMemcpyAsync(c.gather, g.data(), n * 4, hipMemcpyHostToDevice, c.st));
-      dec_logits(c, c.gather, n);
+    dec_forward(c, fwd_prefill(c, B, T, c.hist_tmp, nullptr));
+    logits_in_chunks(c, B * T, [&](int r0, int n) {
       WMX_HIP(hipMemcpy2DAsync(logits_out + (size_t)r0 * V, (size_t)V * 4, c.logits, (size_t)c.ldl * 4, (size_t)V * 4, n,
                                hipMemcpyDeviceToHost, c.st));
-      sync(c);
-    }
+    });
     (void)lens;
   });
 }
@@ -2759,23 +2754,19 @@ wmx_status wmx_ctx_forced_decode(wmx_ctx* x, const int32_t* prefix, const int32_
         WMX_CHECK(p >= 0 && p < R && p / K == r / K, "forced_decode: parent outside the row's window");
         WMX_CHECK(t >= 0 && t < V, "forced_decode: token id");
       }
-    // the layout transcribe() sets up: window b's prefix (prefix_lens[b] ids) left-padded to P; row r of window b
-    // holds it, and its slots < P live in cache row b*K
-    std::vector<int> hist((size_t)R * T, 0), anc((size_t)R * T, 0), pad_row(R), pad_win(B);
+    // transcribe()'s layout (row_layout): window b's prefix (prefix_lens[b] ids) left-padded to P
+    std::vector<std::vector<int>> seqs(B);
     for (int b = 0; b < B; ++b) {
       const int n = prefix_lens ? prefix_lens[b] : P;
       WMX_CHECK(n >= 1 && n <= P, "forced_decode: prefix length");
-      pad_win[b] = P - n;
+      seqs[b].assign(prefix + (size_t)b * P, prefix + (size_t)b * P + n);
     }
-    for (int r = 0; r < R; ++r) {
-      const int b = r / K;
-      pad_row[r] = pad_win[b];
-      for (int i = pad_win[b]; i < P; ++i) hist[(size_t)r * T + i] = prefix[(size_t)b * P + i - pad_win[b]];
-      for (int s = 0; s < T; ++s) anc[(size_t)r * T + s] = s < P ? b * K : r;
-    }
+    RowLayout y = row_layout(c, B, P, seqs);
+    std::vector<int>& hist = y.hist;  // (both advanced on the host by every forced step below)
+    std::vector<int>& anc = y.anc;
     WMX_HIP(hipMemcpyAsync(c.hist, hist.data(), hist.size() * 4, hipMemcpyHostToDevice, c.st));
-    WMX_HIP(hipMemcpyAsync(c.pad_row, pad_row.data(), R * 4, hipMemcpyHostToDevice, c.st));
-    WMX_HIP(hipMemcpyAsync(c.pad_win, pad_win.data(), B * 4, hipMemcpyHostToDevice, c.st));
+    WMX_HIP(hipMemcpyAsync(c.pad_row, y.pad_row.data(), R * 4, hipMemcpyHostToDevice, c.st));
+    WMX_HIP(hipMemcpyAsync(c.pad_win, y.pad_win.data(), B * 4, hipMemcpyHostToDevice, c.st));
     set_slot(c, 0);
     std::vector<float> lg((size_t)R * V);
     auto collect = [&](int step, int nrows, int rep) {  // logits rows [0, nrows) -> top1 / logits of R rows
@@ -2793,16 +2784,7 @@ wmx_status wmx_ctx_forced_decode(wmx_ctx* x, const int32_t* prefix, const int32_
       }
     };
     {  // prefill of the prefix, one sequence per window (cache rows b*K), logits of its last position
-      FwdArgs f;
-      f.rows = B;
-      f.Tn = P;
-      f.rmul = K;
-      f.tok = c.hist;
-      f.tok_ld = (long)K * T;
-      f.pad_seq = c.pad_win;
-      f.prefill = true;
-      f.anc = nullptr;
-      dec_forward(c, f);
+      dec_forward(c, fwd_prefill(c, B, P, c.hist, c.pad_win));
       std::vector<int> g(B);
       for (int b = 0; b < B; ++b) g[b] = b * P + P - 1;
       WMX_HIP(hipMemcpyAsync(c.gather, g.data(), B * 4, hipMemcpyHostToDevice, c.st));
@@ -2825,16 +2807,7 @@ wmx_status wmx_ctx_forced_decode(wmx_ctx* x, const int32_t* prefix, const int32_
       WMX_HIP(hipMemcpyAsync(c.anc, anc.data(), anc.size() * 4, hipMemcpyHostToDevice, c.st));
       set_slot(c, s + 1);
       // the launches of run_step() before its selection
-      FwdArgs f;
-      f.rows = R;
-      f.Tn = 1;
-      f.rmul = 1;
-      f.tok = c.hist;
-      f.tok_ld = T;
-      f.pad_seq = c.pad_row;
-      f.prefill = false;
-      f.anc = c.beam ? c.anc : nullptr;
-      dec_step(c, f);
+      dec_step(c, fwd_step(c, B));
       dec_logits(c, nullptr, R, true);
       collect(i + 1, R, 1);
     }
@@ -2845,12 +2818,8 @@ wmx_status wmx_debug_packed_launch(int M, int N, int K, int64_t part_cap, int sp
   return guard([&] {
     WMX_CHECK(out9 && M >= 1 && N >= 1 && K >= 32 && K % 32 == 0, "debug_packed_launch: arguments");
     // the split count the runtime's callers use: gemm_p (S = 1, epilogue) or gemm_p_part (partials, S >= 2)
-    int S = 1;
-    if (split == 1) {
-      S = packed_splits(M, N, K, part_cap);
-      if (S == 1) S = 2;
-    }
-    const int nct = split == 2 ? 1 : 0;  // 2: the unsplit residual producers of the folded step (gemm_p_resid)
+    const int S = split == 1 ? part_splits(M, N, K, part_cap) : 1;
+    const int nct = split == 2 ? 1 : 0;  // 2: the unsplit residual producers of the mixed step (gemm_p_resid_stats)
     const PackedPlan p = packed_plan(M, N, K, S, nct);
     const PackedExtent e = packed_extent(M, N, K, S, lda, nct);
     const int64_t v[9] = {S, p.MT, p.NCT, p.NW, p.KU, e.w_end, e.a_end, e.part_end, e.stray_ksteps};
@@ -3130,7 +3099,7 @@ static void probe_collect(Ctx& c, double* ms, int* n, double* e2e, int* e2e_n) {
   std::vector<unsigned long long> tk((size_t)kProbeLaunches * T * kProbeWG * 2);
   WMX_HIP(hipStreamSynchronize(c.st));
   WMX_HIP(hipMemcpy(tk.data(), c.probe_buf, tk.size() * 8, hipMemcpyDeviceToHost));
-  // the chain of one layer's launches (dec_step_fast / dec_step_mixed)
+  // the chain of one layer's launches (dec_step_as: the fast form, the mixed form)
   static const int chain_fast[] = {kProbePrev, kProbeQKV, kProbeSelf, kProbeOut, kProbeRedOut, kProbeCrossQ,
                                    kProbeCross, kProbeCrossOut, kProbeRedCrossOut, kProbeFc1, kProbeFc2, kProbeRedFc2};
   static const int chain_mixed[] = {kProbePrev, kProbeQKV, kProbeSelf, kProbeOut, kProbeCross, kProbeCrossOut,
@@ -3284,35 +3253,20 @@ wmx_status wmx_ctx_bench_kernel(wmx_ctx* x, int kernel, int B, int iters, float*
     Model& m = *c.m;
     WMX_CHECK(B >= 1 && B <= c.maxB && iters >= 1, "bench_kernel: args");
     WMX_HIP(hipSetDevice(m.device));
-    const int da = m.d.n_audio_state, dt = m.d.n_text_state, Lt = m.d.n_text_layer, H = m.d.n_text_head;
+    const int da = m.d.n_audio_state, dt = m.d.n_text_state;
     const int R = c.K * B;
+    // a decode form is the step's launch at layer 0, built by the function the step calls; its bytes from the step's table
+    const DecLayer& L0 = m.dec[0];
+    const FwdArgs f = fwd_step(c, B);
+    const StepBytes sb = step_bytes(c, B);
     double by = 0, fl = 0;
     std::function<void()> fn;
     if (kernel == 0) {
-      DecAttnArgs a{};
-      a.q = c.dcq;
-      a.q_ld = dt;
-      a.o = c.dao;
-      a.R = R;
-      a.Tn = 1;
-      a.H = H;
-      a.d = dt;
-      set_cross_images(c, a, 0);
-      a.Tk = 1500;
-      a.rows_per_win = c.K;
-      const double eb = m.kv8 ? 1.0 : 2.0;  // image / weight bytes per element (fp8 decode: 1)
-      by = (double)B * 1500 * 2 * dt * eb + 2.0 * R * dt * 2;
-      fl = 4.0 * R * 1500 * dt;
-      if (c.xq_fused) {  // the decode step's form: the query projection inside (reads LN2 rows + wcq)
-        a.wq = m.kv8 ? reinterpret_cast<const uint16_t*>(m.dec[0].q8cq) : m.dec[0].wcq;
-        a.wq_scale = m.kv8 ? m.dec[0].s8cq : nullptr;
-        a.qin = c.dhb;
-        a.qin_ld = dt;
-        a.qbias = m.dec[0].bcq;
-        by += (double)dt * dt * eb;
-        fl += 2.0 * R * dt * dt;
-      }
-      a.xcnt = c.xa_cnt;
+      // the fast step's cross attention: with c.xq_fused the query projection inside (reads LN2 rows + wcq), else
+      // over the projected queries in c.dcq
+      const DecAttnArgs a = cross_attn_args(c, 0, R, 1, c.K, c.xq_fused ? CrossQ::Fused : CrossQ::Rows);
+      by = sb.cross;
+      fl = 4.0 * R * 1500 * dt + (c.xq_fused ? 2.0 * R * dt * dt : 0.0);
       fn = [&c, a] { launch_cross_attn(c.dt, a, c.xa_ws, c.st); };
     } else if (kernel == 1) {
       const long rows = (long)B * 1500;
@@ -3322,19 +3276,7 @@ wmx_status wmx_ctx_bench_kernel(wmx_ctx* x, int kernel, int B, int iters, float*
         gemm(c, c.ehb, da, m.enc[0].wfc1, da, (int)rows, 4 * da, da, epi(EPI_GELU16, m.enc[0].bfc1, c.ef1, 4 * da));
       };
     } else if (kernel == 2) {
-      AttnArgs a{};
-      a.q = c.eqkv;
-      a.k = c.eqkv + da;
-      a.v = c.eqkv + 2 * da;
-      a.q_ld = a.k_ld = a.v_ld = 3 * da;
-      a.q_bstride = a.k_bstride = a.v_bstride = 1500L * 3 * da;
-      a.o = c.eao;
-      a.o_ld = da;
-      a.o_bstride = 1500L * da;
-      a.B = B;
-      a.H = m.d.n_audio_head;
-      a.Tq = a.Tk = 1500;
-      a.head_stride = 64;
+      const AttnArgs a = enc_attn_args(c, B, false);
       by = (double)B * 1500 * 4 * da * 2;
       fl = 4.0 * B * m.d.n_audio_head * 1500.0 * 1500.0 * 64;
       fn = [&c, a] { launch_attn_encoder(c.dt, a, c.st); };
@@ -3349,28 +3291,14 @@ wmx_status wmx_ctx_bench_kernel(wmx_ctx* x, int kernel, int B, int iters, float*
                       m.mel_off, m.mel_w, m.d.n_mels, c.mel_stats, c.mel_stats_cap, c.mel, c.st);
       };
     } else if (kernel == 4) {
-      by = 4.0 * dt * dt * (m.w8 ? 1 : 2) + (double)R * dt * 2 + (double)R * 4 * dt * 2;
+      by = sb.fc1;
       fl = 2.0 * R * 4 * dt * dt;
-      fn = [&c, &m, R, dt] {
-        gemm_p(c, c.dhb, dt, m.dec[0].wfc1, R, 4 * dt, dt, epi(EPI_GELU16, m.dec[0].bfc1, c.df1, 4 * dt), nullptr,
-               w8_of(m, m.dec[0].q8fc1, m.dec[0].s8fc1));
+      fn = [&c, &m, &L0, R, dt] {
+        gemm_p(c, c.dhb, dt, L0.wfc1, R, 4 * dt, dt, epi(EPI_GELU16, L0.bfc1, c.df1, 4 * dt), nullptr,
+               w8_of(m, L0.q8fc1, L0.s8fc1));
       };
     } else if (kernel == 5) {
-      DecAttnArgs a{};
-      a.q = c.dq;
-      a.q_ld = dt;
-      a.o = c.dao;
-      a.R = R;
-      a.Tn = 1;
-      a.H = H;
-      a.d = dt;
-      a.kc = c.kc;
-      a.vc = c.vc;
-      a.kv_R = c.R;
-      a.anc = c.beam ? c.anc : nullptr;
-      a.anc_ld = c.Tctx;
-      a.pad = c.pad_row;
-      a.slot0 = c.slot;
+      const DecAttnArgs a = self_attn_from_q(c, f, 0);
       int s = 0;
       WMX_HIP(hipMemcpy(&s, c.slot, 4, hipMemcpyDeviceToHost));
       by = (double)R * (s + 1) * dt * 2 * 2;
@@ -3379,16 +3307,9 @@ wmx_status wmx_ctx_bench_kernel(wmx_ctx* x, int kernel, int B, int iters, float*
     } else if (kernel == 11) {
       // decoder fc1 of the mixed step: LN3 folded into the weights, the row statistics merged in the epilogue
       WMX_CHECK(m.mixed, "bench_kernel: the LayerNorm-folded fc1 exists on mixed-step models only");
-      by = 4.0 * dt * dt * 2 + (double)R * dt * 2 + (double)R * 4 * dt * 2;
+      by = sb.fc1;
       fl = 2.0 * R * 4 * dt * dt;
-      fn = [&c, &m, R, dt] {
-        Epi e1 = epi(EPI_LNFOLD_GELU16, nullptr, c.df1, 4 * dt);
-        e1.c1 = m.dec[0].c1fc1;
-        e1.c2 = m.dec[0].c2fc1;
-        e1.stats = c.rstat;
-        e1.stats_ld = dt / 16;
-        gemm_p(c, c.dhb, dt, m.dec[0].ffc1, R, 4 * dt, dt, e1);
-      };
+      fn = [&c, &L0, R, dt] { gemm_p(c, c.dhb, dt, L0.ffc1, R, 4 * dt, dt, epi_fc1_lnfold(c, L0)); };
     } else if (kernel == 6) {
       // the whole encoder (conv front end + every layer + final LN) over B windows: its MFMA work per window
       const double T = 1500, M = m.d.n_mels, Ha = m.d.n_audio_head, La = m.d.n_audio_layer;
@@ -3399,22 +3320,20 @@ wmx_status wmx_ctx_bench_kernel(wmx_ctx* x, int kernel, int B, int iters, float*
     } else if (kernel >= 7 && kernel <= 9) {
       // decode-step projections on packed weights, split-K partial launches: 7 qkv, 8 a d x d projection, 9 fc2
       const int N = kernel == 7 ? 3 * dt : dt, K = kernel == 9 ? 4 * dt : dt;
-      const uint16_t* W = kernel == 7 ? m.dec[0].wqkv : kernel == 8 ? m.dec[0].wo : m.dec[0].wfc2;
-      const DecLayer& L0 = m.dec[0];
+      const uint16_t* W = kernel == 7 ? L0.wqkv : kernel == 8 ? L0.wo : L0.wfc2;
       const W8 w8 = kernel == 7 ? w8_of(m, L0.q8qkv, L0.s8qkv) : kernel == 8 ? w8_of(m, L0.q8o, L0.s8o)
                                                                              : w8_of(m, L0.q8fc2, L0.s8fc2);
       const uint16_t* A = kernel == 9 ? c.df1 : c.dhb;
-      by = (double)N * K * (m.w8 ? 1 : 2) + (double)R * K * 2 + (double)R * N * 2;
+      by = kernel == 7 ? sb.qkv : kernel == 8 ? sb.proj : sb.fc2;
       fl = 2.0 * R * N * K;
       fn = [&c, A, W, R, N, K, w8] { gemm_p_part(c, A, K, W, R, N, K, w8); };
     } else if (kernel == 10) {
       // reduce_ln after a d x d projection: x += bias + sum of its split-K partials; LN(x) -> 16-bit
-      const int S = packed_splits(R, dt, dt, c.part_elems);
-      const int S2 = S == 1 ? 2 : S;
-      by = (double)S2 * R * dt * 4 + 2.0 * R * dt * 4 + (double)R * dt * 2;
+      const int S = part_splits(R, dt, dt, c.part_elems);
+      by = sb.reduce_ln;
       fl = 0;
-      fn = [&c, &m, S2, R, dt] {
-        launch_reduce_ln(c.dt, c.part, S2, m.dec[0].bo, c.dx, m.dec[0].ln2g, m.dec[0].ln2b, c.dhb, R, dt, c.st);
+      fn = [&c, &L0, S, R, dt] {
+        launch_reduce_ln(c.dt, c.part, S, L0.bo, c.dx, L0.ln2g, L0.ln2b, c.dhb, R, dt, c.st);
       };
     } else {
       WMX_CHECK(false, "bench_kernel: unknown kernel");

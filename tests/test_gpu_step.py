@@ -1,6 +1,6 @@
 """GPU parity of the decode STEP at the bench's shapes, and of the decode SEARCH over every step.
 
-What bench.py times per decode step (wmx_runtime.hip dec_step_fast + logits + select/update, replayed from a
+What bench.py times per decode step (wmx_runtime.hip dec_step_as + logits + select/update, replayed from a
 hipGraph) is checked here at the shapes it runs in, against the oracle, in two complementary ways:
 
   * Step kernels, teacher-forced (wmx_ctx_forced_decode): the rows of B windows are fed a fixed token stream
@@ -468,8 +468,8 @@ def test_separate_cross_q_step_parity():
 
 @pytest.mark.timeout(900)
 def test_fast_step_parity():
-    """The fast decode step (WMX_DEC_MIXED=0, wmx_runtime.hip dec_step_fast: every d x d projection split-K with a
-    reduce_ln launch after the out-projection, the cross out-projection and fc2).  The mixed step (dec_step_mixed: the
+    """The fast form of the decode step (WMX_DEC_MIXED=0, wmx_runtime.hip dec_step_as: every d x d projection split-K
+    with a reduce_ln launch after the out-projection, the cross out-projection and fc2).  The mixed form (the
     out-projection and the cross out-projection unsplit with row statistics, LN2 folded into the fused cross-q
     projection of the cross attention, LN3 into fc1's GELU epilogue) is the default for 16-bit models since round 6,
     so the rest of this file runs on it; here its step, search and full-depth tests rerun in a child process on the
@@ -486,6 +486,77 @@ def test_fast_step_parity():
     r = subprocess.run(cmd, cwd=root, env=env, capture_output=True, text=True, timeout=880)
     print(r.stdout[-1500:])
     assert r.returncode == 0, r.stdout[-3000:] + r.stderr[-2000:]
+
+
+# ---------------------------------------------------------------------------------------------------------------
+# wmx_ctx_bench_kernel: every replayed launch form runs and reports its algorithmic bytes and flops
+# ---------------------------------------------------------------------------------------------------------------
+# (bytes, flops) per launch of each form for the micro model (d = 128, 2 heads, 2 + 2 layers, 80 mels), bf16, 2 windows
+# x beam 2 = 4 decode rows, as the library reported them before its forms were rebuilt on the decode step's own launch
+# builders; closed-form in the dims.  self_attn's bytes depend on the slot the transcribe ended at (not pinned).
+BENCH_KERNEL_COST = {
+    "cross_attn": (1570816.0, 3203072.0),
+    "enc_fc1": (3971072.0, 393216000.0),
+    "enc_attn": (3072000.0, 2304000000.0),
+    "logmel": (5760000.0, 321707200.0),
+    "dec_fc1": (136192.0, 524288.0),
+    "encoder": (786432.0, 7630848000.0),
+    "dec_qkv": (102400.0, 393216.0),
+    "dec_proj": (34816.0, 131072.0),
+    "dec_fc2": (136192.0, 524288.0),
+    "reduce_ln": (9216.0, 0.0),
+    "dec_fc1_lnf": (136192.0, 524288.0),
+}
+LNF_REFUSED = "bench_kernel: the LayerNorm-folded fc1 exists on mixed-step models only"
+
+
+def _bench_kernel_ctx():
+    """A micro bf16 context (2 windows x beam 2) after one transcribe of two short windows, so that every buffer a
+    replayed form reads is initialised."""
+    from wmx import engine as E
+    m = E.Model("micro", 0, "bfloat16").init_synthetic(1)
+    ctx = E.Context(m, max_batch=2, beam_size=2, max_new_tokens=8, word_timestamps=True)
+    ctx.transcribe([synth.speech_like(801, 48000), synth.speech_like(802, 32000)])
+    return ctx
+
+
+def test_bench_kernel_forms():
+    """Every form of wmx_ctx_bench_kernel replays (status 0, a finite positive duration) and reports the pinned bytes
+    and flops.  On a model created under WMX_DEC_MIXED=0 (this file rerun by test_fast_step_parity) the LayerNorm-folded
+    fc1 does not exist and its form is refused."""
+    import math
+    import os
+    from wmx import engine as E
+    mixed = os.environ.get("WMX_DEC_MIXED", "1")[:1] != "0"
+    ctx = _bench_kernel_ctx()
+    assert set(E.Context.KERNELS) == set(BENCH_KERNEL_COST) | {"self_attn"}
+    for name in E.Context.KERNELS:
+        if name == "dec_fc1_lnf" and not mixed:
+            with pytest.raises(RuntimeError, match=LNF_REFUSED):
+                ctx.bench_kernel(name, 2, iters=2)
+            continue
+        ms, by, fl = ctx.bench_kernel(name, 2, iters=2)  # (a non-zero status raises)
+        print(f"bench_kernel {name}: {ms:.4f} ms, bytes {by!r}, flops {fl!r}")
+        assert math.isfinite(ms) and ms > 0, (name, ms)
+        if name == "self_attn":
+            assert by > 0, (name, by)
+        else:
+            assert (by, fl) == BENCH_KERNEL_COST[name], (name, by, fl)
+
+
+def test_bench_kernel_lnf_refused_on_fast_step_model():
+    """A model created under WMX_DEC_MIXED=0 (read at model creation, so in a child process) has no LayerNorm-folded
+    fc1: that form is refused with its message; the forms the fast step does run still replay."""
+    import os
+    import subprocess
+    import sys
+
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    env = dict(os.environ, WMX_DEC_MIXED="0")
+    cmd = [sys.executable, "-m", "pytest", "-x", "-q", "-m", "gpu", "-p", "no:cacheprovider",
+           "-k", "test_bench_kernel_forms", "tests/test_gpu_step.py"]
+    r = subprocess.run(cmd, cwd=root, env=env, capture_output=True, text=True, timeout=120)
+    assert r.returncode == 0 and "1 passed" in r.stdout, r.stdout[-3000:] + r.stderr[-2000:]
 
 
 # ---------------------------------------------------------------------------------------------------------------

@@ -4,7 +4,7 @@ bench.py's in-situ `roofline`).
 Every decode step on a queue is  embed_ln, then per decoder layer  [packed qkv, self attention, packed out,
 reduce_ln, (packed cross-q,) cross attention, packed cross-out, reduce_ln, packed fc1, packed fc2, reduce_ln]
 (no cross-q launch when the cross attention projects its own queries, the default: detected from the count),
-then the packed logits GEMM and the selection kernels (wmx_runtime.hip dec_step_fast / run_step).  The packed
+then the packed logits GEMM and the selection kernels (wmx_runtime.hip dec_step_as / run_step).  The packed
 GEMM launches of a step are labelled by their position; durations are averaged per label over every decode step
 of every queue; algorithmic bytes per launch are those bench.py uses (weights + 16-bit activations in and out).
 
