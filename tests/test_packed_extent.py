@@ -59,7 +59,7 @@ def decode_launches(d, B, K):
 CONTEXTS = [(B, K) for B in (1, 2, 3, 4, 5, 8, 16, 20) for K in (1, 5)]
 
 
-@pytest.mark.parametrize("name", ["micro", "tiny", "base", "large-v3"])
+@pytest.mark.parametrize("name", ["micro", "tiny", "base", "small", "medium", "large-v3", "large-v3-turbo"])
 def test_packed_launches_stay_inside_their_buffers(name):
     d = E.MODEL_DIMS[name]
     n = 0
@@ -80,6 +80,43 @@ def test_packed_launches_stay_inside_their_buffers(name):
                 assert e["S"] <= 8, where
             n += 1
     print(name, "packed launches checked:", n)
+
+
+def plans(name):
+    """The (split mode, S, MT, NCT, NW, KU) of every packed launch of one model over all CONTEXTS."""
+    d = E.MODEL_DIMS[name]
+    out = set()
+    for B, K in CONTEXTS:
+        part_cap = B * K * d.n_text_state * 48
+        for _, M, N, Kd, split, lda, _, _ in decode_launches(d, B, K):
+            e = launch(M, N, Kd, part_cap, split, lda)
+            out.add((split,) + tuple(e[k] for k in ("S", "MT", "NCT", "NW", "KU")))
+    return out
+
+
+def test_small_and_medium_own_plans_in_every_split_mode():
+    """Why tests/test_gpu_widths.py exists.  packed_nw chooses 8 waves for 17 to 32 k-steps per K slice (or where 16
+    waves would not fit the LDS budget).  An unsplit K = d launch has K / 32 = 24 or 32 k-steps at d = 768 and 1024
+    alone (base: 16 -> 4 waves, large-v3: 40 -> 16 waves), so in the unsplit modes 0 and 2 small and medium between them
+    have NW = 8 plans (split mode, S, MT, NCT, NW, KU) that no launch of micro, tiny, base or large-v3 (the widths the
+    other GPU modules run) ever takes.  NW = 8 plans that those widths do reach are not counted.  In split mode 1 the
+    split leaves small and medium at most 16 k-steps per slice, so they run 4 waves there (of these models only
+    large-v3 splits into 8-wave slices); what they own in that mode are split counts: plans with S = 5, 6 or 7.
+    If a retuned packed_nw / packed_splits empties one of these sets, the message says where to look."""
+    elsewhere = set().union(*(plans(n) for n in ("micro", "tiny", "base", "large-v3")))
+    own = {name: plans(name) for name in ("small", "medium")}
+    for name in own:
+        print(name, "plans:", len(own[name]), "of which no other width reaches:", len(own[name] - elsewhere))
+    only_here = (own["small"] | own["medium"]) - elsewhere
+    for split in (0, 1, 2):
+        mine = sorted(p for p in only_here if p[0] == split and (p[4] == 8 or split == 1))
+        print("split mode", split, "plans (split, S, MT, NCT, NW, KU) of d = 768 / 1024 alone"
+              + ("" if split == 1 else " with NW = 8") + ":", mine)
+        assert mine, (f"split mode {split}: small / medium (d = 768 / 1024) no longer have packed plans of their own "
+                      f"(NW = 8 in modes 0 and 2); see which widths tests/test_gpu_widths.py must cover now",
+                      sorted(own["small"] | own["medium"]))
+        if split == 1:
+            assert {p[1] for p in mine} >= {5, 6, 7}, mine
 
 
 def test_extent_walker_is_tight():
